@@ -4,11 +4,9 @@
 A "step" is one MCMC transition (walnuts.hpp:520-563) of EVERY chain.  One launch of the persistent transition
 kernel runs `--transitions-per-launch` consecutive steps (default 8: the workgroup that fetched a chain runs that
 many transitions of it back to back -- the chains are independent -- so the launch and its tail, the last chains
-finishing while the chip drains, are paid once per launch; every transition's draw plane is written).  `--steps` and
-`--warmup` are MINIMA: the timed region holds whole launches only and at least `--min-launches` (12) of them -- the
-first dispatches after a join run 10-50 % off steady state --, so the driver's `--steps 20 --warmup 5` times 96
-transitions after 8 untimed ones; the line's `steps` / `warmup` are the transitions actually run, `steps_requested` /
-`warmup_requested` the command line's (`--exact-steps`: exactly K, the last launch short).  Default workload =
+finishing while the chip drains, are paid once per launch; every transition's draw plane is written).  The timed
+region runs exactly `--steps` transitions after exactly `--warmup` untimed ones (when K is not a multiple of the
+transitions per launch, the last launch is short); `ms_per_step` = the region's wall time / K.  Default workload =
 BASELINE.json's headline: 65 536 chains x 1 024-dim standard normal, default SamplingConfig, parameters adapted by
 `--adapt-iters` on-device warmup transitions (untimed), then the untimed and the timed sampling transitions.  Inputs are
 generated on the device (counter-based stream) and are resident in HBM when the timed region starts.
@@ -31,6 +29,10 @@ transition.
 
 Rank 0 prints ONE JSON line.  `value` = gradient evaluations of all chains on all ranks in the timed region
 / max-over-ranks wall time.
+
+`--dump-outputs DIR`: after the timed region, rank 0 writes what the timed path computed in its last step as float64
+.npy files (`dump_outputs`), so that two builds run with the same arguments -- hence the same seeded inputs -- can be
+compared output for output.
 
 `roofline` describes the dominant kernel, timed with HIP events on the stream it is launched on:
   * register kernels (D <= 8192: the trajectory end never leaves the chip): bound "fp64-valu".  `achieved` = useful
@@ -121,15 +123,17 @@ def parse():
                          "one pair around the timed region")
     ap.add_argument("--phase", default="sampling", choices=["sampling", "warmup"],
                     help="which transition kind is timed")
-    ap.add_argument("--min-launches", type=int, default=12,
-                    help="the timed region holds at least this many whole launches (--steps is a minimum)")
-    ap.add_argument("--exact-steps", action="store_true",
-                    help="time exactly --steps transitions (the last launch short) instead of whole launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's draws and log densities (a fixed, seeded sample of the chains "
+                         "when all of them would exceed 64 MB) as DIR/<name>.npy")
     ap.add_argument("--legs", default="auto",
                     help="auto: the default headline run on one GPU also measures BASELINE configs #2-#4 and the headline's "
                          "warmup phase (short legs under \"configs\" of the same JSON line); none; or a comma list of "
                          "cfg2,cfg3,cfg4,headline_warmup")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def model_setup(name, D):
@@ -205,6 +209,30 @@ def measured_traffic(args, D, chains_local, transitions_per_average_launch):
                                                         "; same source hash, same workload" + groups + ")")
             stale = f"stale PMC entry refused (recorded for csrc {e.get('csrc_sha')}, this build is {sha})"
     return None, stale or "this workload was not profiled"
+
+
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(path, draws, logp, chain0, seed):
+    """--dump-outputs: what the timed path computed in its last step on this rank, as float64 .npy files under `path`:
+    `draws` [chains, D] (each chain's draw of that step), `logp` [chains] (its log density) and `chains` [chains] (its
+    global chain id).  All chains when they fit in DUMP_LIMIT_BYTES, else a sample of them drawn with `seed` (the same
+    rows for the same arguments; a draw longer than the limit keeps its first coordinates).  Returns what was written."""
+    import torch
+
+    C, D = draws.shape
+    room = (DUMP_LIMIT_BYTES - 3 * 4096) // 8     # float64 values, after three generous .npy headers
+    cols = min(D, room - 2)
+    rows = min(C, room // (cols + 2))
+    idx = np.arange(C) if rows == C else np.sort(np.random.default_rng(seed).choice(C, rows, replace=False))
+    sel = torch.from_numpy(idx).to(draws.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "draws.npy"), draws[sel, :cols].to(torch.float64).cpu().numpy())
+    np.save(os.path.join(path, "logp.npy"), np.asarray(logp, dtype=np.float64)[idx])
+    np.save(os.path.join(path, "chains.npy"), (chain0 + idx).astype(np.float64))
+    return {"dir": path, "files": ["draws.npy", "logp.npy", "chains.npy"], "chains": int(rows), "of_chains": int(C),
+            "dims": int(cols), "of_dims": int(D), "dtype": "float64"}
 
 
 def host_cores():
@@ -533,7 +561,7 @@ def main():
             out["configs"] = {}
             for name, spec in legs.items():
                 t_leg = time.perf_counter()
-                leg_args = argparse.Namespace(**{**vars(args), **spec})
+                leg_args = argparse.Namespace(**{**vars(args), **spec, "dump_outputs": None})
                 try:
                     rec = run_job(leg_args, rank, local_rank, world, dist, cpu=False)
                     out["configs"][name] = {k: rec[k] for k in ("value", "unit", "steps", "warmup", "ms_per_step", "config",
@@ -670,16 +698,7 @@ def run_job(args, rank, local_rank, world, dist, cpu=True):
         eng.synchronize()
         torch.cuda.synchronize()
 
-    # --steps / --warmup are MINIMA: the timed region holds whole launches only (T transitions each), and at least
-    # --min-launches of them -- the first dispatches after a join run 10-50 % off steady state, and a region of 8+8+4
-    # transitions is a fragile sample.  `steps` / `warmup` in the line are the transitions actually run;
-    # `steps_requested` / `warmup_requested` what the command line asked for.  (--exact-steps: exactly K, last launch short.)
-    steps_requested, warmup_requested = args.steps, args.warmup
-    if args.exact_steps:
-        n_steps, n_warm = args.steps, args.warmup
-    else:
-        n_steps = max(-(-args.steps // T), args.min_launches) * T
-        n_warm = -(-args.warmup // T) * T
+    n_steps, n_warm = args.steps, args.warmup   # exactly; run_steps makes the last launch short when T does not divide
     for i in range(0, args.adapt_iters, T):
         eng.warmup_steps(min(T, args.adapt_iters - i))
     if args.phase == "sampling":
@@ -701,6 +720,13 @@ def run_job(args, rank, local_rank, world, dist, cpu=True):
     fence()
     elapsed = time.perf_counter() - t0
     g_after = eng.total_grad_evals()
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the last launch's last draw plane is the last timed step's (the N > 1 legs below overwrite the buffers)
+        last = (n_steps - 1) // T
+        block = gather.buffer(last)
+        dumped = dump_outputs(args.dump_outputs, (block[(n_steps - 1) % T] if T > 1 else block)[:C], eng.logp(),
+                              chain0, args.seed)
     ktimes = eng.kernel_times_ms() if per_launch else [region_total_ms / max(region_launches, 1)]
     groups = eng.chain_groups
     timing_method = ("one pair of HIP events per launch" if per_launch else
@@ -801,8 +827,6 @@ def run_job(args, rank, local_rank, world, dist, cpu=True):
             "n_gpus": world,
             "steps": n_steps,
             "warmup": n_warm,
-            "steps_requested": steps_requested,
-            "warmup_requested": warmup_requested,
             "ms_per_step": elapsed / max(n_steps, 1) * 1e3,
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -830,6 +854,8 @@ def run_job(args, rank, local_rank, world, dist, cpu=True):
             },
             "roofline": roofline,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if legs is not None:
             full_ms = elapsed / max(n_steps, 1) * 1e3
             comp_ms = legs["compute_s"] / max(n_steps, 1) * 1e3

@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export WALNUTS_AMD_CHAIN_GROUPS=1   # (one dispatch per launch: the per-launch counter values below are one kernel's)
 # (steps and warmup are multiples of the transitions per launch: every profiled dispatch is a full launch)
-ARGS="--no-cpu-baseline --no-parity-gate --legs none --min-launches 2 --steps 16 --warmup 8 --adapt-iters 100 $*"
+ARGS="--no-cpu-baseline --no-parity-gate --legs none --steps 16 --warmup 8 --adapt-iters 100 $*"
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" \

@@ -19,6 +19,8 @@ def build_surface_library(lib_path: str, tag: str) -> str:
     if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(f) for f in [src, lib_path] + hdrs):
         return out
     libdir = os.path.dirname(lib_path)
+    tmp = os.path.join(HERE, f"libcpp_surface_{tag}.{os.getpid()}.so")
     subprocess.check_call(["g++", "-std=c++20", "-O1", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", "-I",
-                           os.path.join(ROOT, "include"), src, "-o", out, lib_path, f"-Wl,-rpath,{libdir}", "-pthread"])
+                           os.path.join(ROOT, "include"), src, "-o", tmp, lib_path, f"-Wl,-rpath,{libdir}", "-pthread"])
+    os.replace(tmp, out)   # (whole or not at all: test processes may build side by side)
     return out

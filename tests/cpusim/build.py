@@ -18,6 +18,12 @@ def build(force: bool = False) -> str:
         os.path.join(HERE, "wn_cpusim.h")]
     if not force and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
         return OUT
+    # every file is written under a name of this process's own and then renamed into place: test processes running
+    # side by side may build at the same time, and none may link or load another's half-written file
+    def own(f):   # (the extension stays last: an interrupted build leaves nothing the ignore patterns miss)
+        base, ext = os.path.splitext(f)
+        return f"{base}.{os.getpid()}{ext}"
+
     objs = []
     procs = []
     for s in srcs:
@@ -25,11 +31,13 @@ def build(force: bool = False) -> str:
         objs.append(o)
         procs.append(subprocess.Popen(
             ["g++", "-x", "c++", "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-pthread", "-DWN_CPU_SIM",
-             "-DWN_SIM_GEOMETRIES", "-I", HERE, "-I", CSRC, "-c", s, "-o", o]))
+             "-DWN_SIM_GEOMETRIES", "-I", HERE, "-I", CSRC, "-c", s, "-o", own(o)]))
     for p in procs:
         if p.wait() != 0:
             raise RuntimeError("cpusim compile failed")
-    subprocess.check_call(["g++", "-shared", "-pthread", "-o", OUT] + objs)
+    subprocess.check_call(["g++", "-shared", "-pthread", "-o", own(OUT)] + [own(o) for o in objs])
+    for f in objs + [OUT]:
+        os.replace(own(f), f)
     return OUT
 
 

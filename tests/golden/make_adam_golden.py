@@ -39,6 +39,15 @@ for ps in param_sets:
                        wno._p(alphas), n, wno._p(out))
         cases.append(dict(params=ps, alphas=[float.hex(float(a)) for a in alphas],
                           steps=[float.hex(float(s)) for s in out]))
+# the long sequence of test_oracle_kat.py::test_adam_matches_live_reference_build_when_present: 500 uniform rates
+# (seed 7) from step 0.7 with the WarmupConfig defaults
+ps = dict(param_sets[0], step_init=0.7)
+alphas = np.random.default_rng(7).uniform(0, 1, 500)
+out = np.empty(alphas.size)
+L.adam_ref_run(ps["step_init"], ps["target"], ps["lr"], ps["b1"], ps["b2"], ps["eps"], ps["decay"],
+               wno._p(alphas), alphas.size, wno._p(out))
+cases.append(dict(name="long_uniform_seed7", params=ps, alphas=[float.hex(float(a)) for a in alphas],
+                  steps=[float.hex(float(s)) for s in out]))
 path = os.path.join(ROOT, "tests", "golden", "adam_reference.json")
 json.dump(dict(source="reference include/walnutpie/adam.hpp compiled by oracle/Makefile (target ref)",
                cases=cases), open(path, "w"), indent=0)
