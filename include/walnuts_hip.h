@@ -146,6 +146,35 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
     int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
     int thin, wn_chains** chains_out, WalnutpyError** err);
 
+/* walnutpie_sample_device / _resident for a model conditioned on data (walnuts_amd/csrc/wn_model_api.h, kUsesData:
+ * MODEL_LINEAR_REGRESSION, MODEL_LOGISTIC_REGRESSION, or a model of your own): x [num_obs][num_params] row-major and
+ * y [num_obs], host pointers, checked and copied to the device once (not retained).  Everything else as the calls
+ * above.  One device only: the multi-device and reference-stream entry points take no data. */
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_data(
+    int model, const double* model_params, int num_params, const double* x, const double* y, int num_obs,
+    const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    WalnutpyError** err);
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_data_resident(
+    int model, const double* model_params, int num_params, const double* x, const double* y, int num_obs,
+    const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    int thin, wn_chains** chains_out, WalnutpyError** err);
+
 /* walnutpie_sample_device over SEVERAL devices of the node ("one process, one driver thread +
  * stream per GPU").  devices[num_devices]: HIP ordinals; shard s -- a contiguous block of the global chain ids, sizes
  * differing by at most one -- runs on devices[s] with its own host thread, engine and stream and writes its own slice
@@ -293,7 +322,20 @@ WALNUTS_HIP_EXPORT int wn_geometry_candidates(int num_params, int waves_per_chai
 /* model_params: host pointer (copied). */
 WALNUTS_HIP_EXPORT int wn_engine_create(wn_engine** out, int model, int num_params, const double* model_params,
                                         size_t num_chains, const wn_config* cfg, WalnutpyError** err);
+/* A model conditioned on data (kUsesData): the observations x [num_obs][num_params] row-major and y [num_obs] (host
+ * pointers, checked -- finite; the model's own checks, e.g. y in {0, 1} for logistic_regression -- and copied to the
+ * device in the layout of a theta row; not retained; freed by wn_engine_destroy).  A data model created through
+ * wn_engine_create, data for a model without kUsesData, and a data model outside one wavefront per chain
+ * (num_params > 1024, or an explicit wider geometry) are `config` errors. */
+WALNUTS_HIP_EXPORT int wn_engine_create_with_data(wn_engine** out, int model, int num_params, const double* model_params,
+                                                  const double* x, const double* y, int num_obs, size_t num_chains,
+                                                  const wn_config* cfg, WalnutpyError** err);
 WALNUTS_HIP_EXPORT void wn_engine_destroy(wn_engine* e);
+/* The engine's model at positions the caller chooses: theta [C*D] in, logp_out [C] and grad_out [C*D] out (host
+ * pointers), in the engine's arithmetic mode -- the reference's logp_grad(theta) -> (logp, grad) for every chain at
+ * once.  No chain state is read or changed. */
+WALNUTS_HIP_EXPORT int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* grad_out,
+                                      WalnutpyError** err);
 
 /* InitConfig (config.hpp:74-185): positions [C*D], masses [C*D] (masses, not inverse
  * masses), step sizes [C]; host pointers. */

@@ -74,6 +74,15 @@ SYMBOLS = [
      [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
       _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
       _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
+    # the data-model siblings: x, y, num_obs after num_params
+    ("walnutpie_sample_device_data", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
+    ("walnutpie_sample_device_data_resident", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
     ("walnutpie_sample_device_multi", _i32,
      [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
       _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
@@ -103,7 +112,9 @@ SYMBOLS = [
     ("wn_geometry_for_model", _i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _errpp]),
     ("wn_geometry_candidates", _i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int), _i32, C.POINTER(C.c_int), _errpp]),
     ("wn_engine_create", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _sz, C.POINTER(Config), _errpp]),
+    ("wn_engine_create_with_data", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32, _sz, C.POINTER(Config), _errpp]),
     ("wn_engine_destroy", None, [_vp]),
+    ("wn_engine_eval", _i32, [_vp, _dp, _dp, _dp, _errpp]),
     ("wn_engine_set_positions", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_set_masses", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_set_step_sizes", _i32, [_vp, _dp, _errpp]),

@@ -1,0 +1,154 @@
+// models/glm.h -- Bayesian generalised linear models on an observation block the engine keeps in HBM (wn_model_api.h,
+// kUsesData): linear regression (unit-variance normal noise) and logistic regression, one template over the link.
+//
+//   eta = X theta,  prior theta_i ~ normal(0, s_i^2)  (model_params: the prior variances s^2)
+//   linear_regression:    logp = -1/2 sum_n (y_n - eta_n)^2             - 1/2 sum_i theta_i^2 / s_i^2
+//                         grad = X^T (y - eta)                            - theta / s^2
+//   logistic_regression:  logp = sum_n (y_n eta_n - softplus(eta_n))     - 1/2 sum_i theta_i^2 / s_i^2
+//                         grad = X^T (y - sigmoid(eta))                   - theta / s^2
+// (constants dropped.  Another noise level sigma for the linear model: pass x / sigma and y / sigma.)
+//
+// One pass over X per gradient evaluation.  The chain's lane `tid` holds EPL coordinates of theta, and row n of X is
+// laid out the same way, so a row is EPL / 2 16-byte loads per lane and its product with theta is EPL lane-local
+// multiply-adds.  What costs is the reduction of that partial dot product over the wavefront and the link function,
+// so the rows are taken in BLOCKS of B = max(2, 32 / EPL) (the block's rows stay in registers: 32 doubles per lane):
+//   1. for each pair of rows (n0 + 2k, n0 + 2k + 1) of the block, in order: the lanes' partial dot products (slot
+//      order 0..EPL-1, Cx::mad) go through ONE packed butterfly (wave_sum_packed: offsets 32, 1, 2, 4, 8, 16) and
+//      eta of row n0 + k lands in lane k (set_lane);
+//   2. lanes 0..B-1 evaluate the link of their row at once (one vector evaluation for B rows): the residual
+//      r = y - mean(eta) and the row's log-likelihood term, which lane k adds to its own running sum;
+//   3. the residuals are broadcast back one row at a time (lane_value) and g[j] += x_row[j] * r, rows in order.
+// The log-likelihood terms of lane k (rows n = n0 + k of every block, blocks in order) are added to the lane's prior
+// partial after the last block; the kernels' own reduction of `acc` then sums the lanes in its fixed order.  A last,
+// partial block reads no row at or beyond num_obs: its missing rows are zeros and their residuals and terms are
+// masked to 0.  The CPU emulation runs the same source with the same butterfly order, so the bits agree.
+//
+// Arithmetic: the prior variances arrive as reciprocals (host_params, as the diagonal normal's); the logistic mean is
+// one true division per block-row evaluation, 1 / (1 + exp(-|eta|)), and softplus(eta) = max(eta, 0) +
+// log(1 + exp(-|eta|)) never overflows.  exp / log are wnd::dexp / wnd::dlog with per-lane arguments (gather tables).
+#pragma once
+
+#include <cmath>
+#include <stdexcept>
+#include <string>
+
+#include "../wn_model_api.h"
+
+namespace wn {
+
+struct IdentityLink {
+  // r = y - eta; ll += -1/2 r^2
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static double term(double eta, double y, double& r, double ll, const Tab&) {
+    r = y - eta;
+    return Cx::mad(-0.5 * r, r, ll);
+  }
+  static void check_y(double) {}
+};
+
+struct LogitLink {
+  // r = y - sigmoid(eta); ll += y eta - softplus(eta)
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static double term(double eta, double y, double& r, double ll, const Tab& tab) {
+    const double a = __builtin_fabs(eta);
+    const double e = wnd::dexp(-a, tab);  // in (0, 1]
+    const double d = 1.0 / (1.0 + e);
+    const double mu = eta >= 0.0 ? d : e * d;
+    const double sp = (eta > 0.0 ? eta : 0.0) + wnd::dlog(1.0 + e, tab);
+    r = y - mu;
+    return Cx::mad(y, eta, ll) - sp;
+  }
+  static void check_y(double y) {
+    if (!(y == 0.0 || y == 1.0)) throw std::invalid_argument("logistic_regression needs every y in {0, 1}");
+  }
+};
+
+template <class Link>
+struct GlmModel {
+  static constexpr bool kUsesParams = true;  // prior variances s^2 [num_params]
+  static constexpr bool kUsesData = true;
+  static constexpr bool kElementwise = false;
+  static constexpr bool kGradIsNegTheta = false;
+  static constexpr bool kCheapGrad = false;
+  __device__ __forceinline__ static double grad_elem(double, double) { return 0.0; }
+  struct Aux {};
+
+  template <int EPL>
+  static constexpr int kBlock = EPL >= 16 ? 2 : 32 / EPL;  // rows per block (registers: 32 doubles per lane)
+
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void eval(Cx& cx, const double (&th)[EPL], double (&g)[EPL],
+                                              const double (&rs2)[EPL], Aux&, double& acc) {
+    static_assert(Cx::L == 64, "data models run one wavefront per chain");
+    constexpr int B = kBlock<EPL>;
+    static_assert(B % 2 == 0 && B <= 64, "rows are reduced in pairs");
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      g[j] = -th[j] * rs2[j];
+      acc = Cx::mad(-0.5 * th[j] * th[j], rs2[j], acc);
+    }
+    const int N = cx.num_obs();
+    const int me = opaque_lane_id();
+    double ll = 0.0;  // this lane's log-likelihood terms
+    for (int n0 = 0; n0 < N; n0 += B) {
+      double x[B][EPL];
+      double eta = 0.0;
+#pragma unroll
+      for (int k = 0; k < B; ++k) {
+        if (n0 + k < N) {
+          cx.load_row(n0 + k, x[k]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < EPL; ++j) x[k][j] = 0.0;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < B; k += 2) {
+        double da = 0.0, db = 0.0;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) {
+          da = Cx::mad(x[k][j], th[j], da);
+          db = Cx::mad(x[k + 1][j], th[j], db);
+        }
+        const double packed = wave_sum_packed(da, db);  // row k's sum in lanes 0-31, row k + 1's in lanes 32-63
+        set_lane(eta, uni(packed), k);
+        set_lane(eta, lane_value(packed, 32), k + 1);
+      }
+      const bool mine = me < B && n0 + me < N;
+      const double y = mine ? cx.obs_y(n0 + me) : 0.0;
+      double r;
+      const double ll_new = Link::template term<Cx>(eta, y, r, ll, cx.gather_tab());
+      ll = mine ? ll_new : ll;
+      r = mine ? r : 0.0;
+#pragma unroll
+      for (int k = 0; k < B; ++k) {
+        const double rk = lane_value(r, k);
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) g[j] = Cx::mad(x[k][j], rk, g[j]);
+      }
+    }
+    acc = acc + ll;
+  }
+  __device__ __forceinline__ static double finish(double sum, const Aux&, int) { return sum; }
+
+  // host side: the prior variances -> their reciprocals (rounded once), and the observations' checks
+  static void host_params(double* s2, int num_params) {
+    for (int i = 0; i < num_params; ++i) {
+      if (!(s2[i] > 0) || !std::isfinite(s2[i])) throw std::invalid_argument("prior variances must be positive and finite");
+      s2[i] = 1.0 / s2[i];
+    }
+  }
+  static void host_data(const double*, const double* y, int num_obs, int) {
+    for (int n = 0; n < num_obs; ++n) Link::check_y(y[n]);
+  }
+  static void validate(int num_params) {
+    if (num_params > 1024)
+      throw std::invalid_argument("a data model supports 1 <= num_params <= 1024 (one wavefront per chain), got " +
+                                  std::to_string(num_params));
+  }
+};
+
+using LinearRegressionModel = GlmModel<IdentityLink>;
+using LogisticRegressionModel = GlmModel<LogitLink>;
+
+}  // namespace wn

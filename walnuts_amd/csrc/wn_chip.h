@@ -117,6 +117,12 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   // ---- model context (what Model::eval sees) ------------------------------------------------------
   __device__ __forceinline__ int index(int j) const { return ((j >> 1) * L + tid) * 2 + (j & 1); }
   __device__ __forceinline__ bool valid(int j) const { return index(j) < P.dim; }
+  // data models (wn_model_api.h, kUsesData): the engine's read-only observation block, rows laid out like theta
+  __device__ __forceinline__ int num_obs() const { return P.num_obs; }
+  __device__ __forceinline__ void load_row(int n, double (&x)[EPL]) const {
+    vload(P.data_x + static_cast<long long>(n) * kDp, x);
+  }
+  __device__ __forceinline__ double obs_y(int n) const { return P.data_y[n]; }
   template <int S>
   __device__ __forceinline__ double G(int j) const {
     return kNoGrad ? Model::grad_elem(th[S][j], mp[j]) : g[S][j];

@@ -62,6 +62,8 @@ struct wn_engine {
   DevBuf<double> theta, mass, inv_mass, chol_mass, draw_mean, draw_ssd, score_mean, score_ssd;
   DevBuf<double> step_init, step_size, adam, est_weight, mm_state, logp, model_params, arena, z_buf, u_buf;
   DevBuf<double> lp_stats, mon_partial, mon_out, mon_colsum, mon_rel_mass, mon_rel_step;
+  DevBuf<double> data_x, data_y;  // a data model's observations: [num_obs][Dp] (rows padded with zeros), [num_obs]
+  int num_obs = 0;
   DevBuf<int32_t> min_micro, depth, rng_draws, failed_ext;
   DevBuf<int64_t> grad_evals;
   DevBuf<uint32_t> counter, error_flags;
@@ -272,6 +274,10 @@ struct wn_engine {
     P.est_mode = (warm && est_pending) ? 1 : 0;
     P.work_counter = counter.p;
     P.error_flags = error_flags.p;
+    P.data_x = data_x.p;
+    P.data_y = data_y.p;
+    P.num_obs = num_obs;
+    P.data_stride = Dp;
     return P;
   }
 
@@ -409,8 +415,15 @@ int required_pool(const wn_config& c) {
   return 4 + 3 * levels + 3 + 3 + 2;
 }
 
+// a data model's observations as the caller hands them over (host memory, row-major; not retained)
+struct HostData {
+  const double* x;  // [num_obs][num_params]
+  const double* y;  // [num_obs]
+  int num_obs;
+};
+
 void build_engine(wn_engine& e, int model, int num_params, const double* model_params, size_t num_chains,
-                  const wn_config& cfg) {
+                  const wn_config& cfg, const HostData* data = nullptr) {
   if (num_params < 1) throw std::invalid_argument("num_params must be positive");
   if (num_chains < 1) throw std::invalid_argument("num_chains must be positive");
   if (!wn::registry_error().empty()) throw std::invalid_argument(wn::registry_error());
@@ -425,6 +438,21 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   if (ops.uses_params && model_params == nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model needs a parameter vector of num_params doubles");
   ops.validate(num_params);
+  if (ops.uses_data && data == nullptr)
+    throw std::invalid_argument(std::string(ops.name) + " model is conditioned on data: create it with "
+                                "wn_engine_create_with_data (x [num_obs][num_params], y [num_obs])");
+  if (!ops.uses_data && data != nullptr)
+    throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
+  if (data != nullptr) {
+    if (data->num_obs < 1) throw std::invalid_argument("num_obs must be positive");
+    if (data->x == nullptr || data->y == nullptr) throw std::invalid_argument("null data argument");
+    const size_t n = static_cast<size_t>(data->num_obs) * static_cast<size_t>(num_params);
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(data->x[i])) throw std::invalid_argument("data x must be finite");
+    for (int i = 0; i < data->num_obs; ++i)
+      if (!std::isfinite(data->y[i])) throw std::invalid_argument("data y must be finite");
+    ops.host_data(data->x, data->y, data->num_obs, num_params);
+  }
 
   e.model = model;
   e.D = num_params;
@@ -434,6 +462,9 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   e.geo = wn::choose_geometry(num_params, cfg.waves_per_chain, cfg.elems_per_lane, ops.uses_params, ops.preferred_epl(num_params),
                               ops.hold_tiles(wn::kHeldWaves), ops.register_dim_limit);
   e.Dp = wn::padded_dim(e.geo, num_params);
+  if (ops.uses_data && (e.geo.mem || e.geo.nw != 1))
+    throw std::invalid_argument(std::string(ops.name) + ": a data model runs one wavefront per chain (num_params <= 1024, "
+                                "waves_per_chain 0 or 1, elems_per_lane 0, 2, 4, 8 or 16)");
   e.use_device();
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, e.device));
@@ -568,6 +599,18 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     HIP_OK(hipMemcpyAsync(e.model_params.p, mp.data(), mp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
     HIP_OK(hipStreamSynchronize(e.stream));
   }
+  if (data != nullptr) {
+    // rows padded to Dp with zeros: the layout of a theta row (lane tid's slot j holds coordinate index(j))
+    const size_t N = static_cast<size_t>(data->num_obs);
+    std::vector<double> xp(N * static_cast<size_t>(e.Dp), 0.0);
+    for (size_t n = 0; n < N; ++n) std::memcpy(&xp[n * e.Dp], data->x + n * num_params, sizeof(double) * num_params);
+    e.data_x.alloc(xp.size());
+    e.data_y.alloc(N);
+    e.num_obs = data->num_obs;
+    HIP_OK(hipMemcpyAsync(e.data_x.p, xp.data(), xp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
+    HIP_OK(hipMemcpyAsync(e.data_y.p, data->y, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
+    HIP_OK(hipStreamSynchronize(e.stream));
+  }
   wn::prepare_kernels(model, e.geo, e.smem);
 }
 
@@ -595,6 +638,10 @@ void run_init(wn_engine& e, bool pos, bool masses, bool step, double scale, doub
   Q.step_seed = step_seed;
   Q.pos_chain_offset = pos_off;
   Q.step_chain_offset = step_off;
+  Q.data_x = e.data_x.p;
+  Q.data_y = e.data_y.p;
+  Q.num_obs = e.num_obs;
+  Q.data_stride = e.Dp;
   const int grid = e.geo.mem ? e.grid : static_cast<int>(std::min<size_t>(e.C, static_cast<size_t>(e.num_cus) * 8));
   wn::launch_init(e.model, e.geo, grid, wn::transition_smem_bytes(e.geo.nw, 0, e.Dp), e.stream, Q);
   HIP_OK(hipGetLastError());
@@ -763,7 +810,57 @@ int wn_engine_create(wn_engine** out, int model, int num_params, const double* m
     *out = e.release();
   });
 }
+int wn_engine_create_with_data(wn_engine** out, int model, int num_params, const double* model_params,
+                               const double* x, const double* y, int num_obs, size_t num_chains, const wn_config* cfg,
+                               WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (out == nullptr || cfg == nullptr) throw std::invalid_argument("null argument");
+    const HostData data{x, y, num_obs};
+    auto e = std::make_unique<wn_engine>();
+    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
+    *out = e.release();
+  });
+}
 void wn_engine_destroy(wn_engine* e) { delete e; }
+
+int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* grad_out, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (e == nullptr || theta == nullptr || logp_out == nullptr || grad_out == nullptr)
+      throw std::invalid_argument("null argument");
+    const size_t C = e->C, D = static_cast<size_t>(e->D), Dp = static_cast<size_t>(e->Dp);
+    e->use_device();
+    // the engine's own planes stay untouched: positions and gradients go through buffers of this call
+    DevBuf<double> th, grad, lp;
+    th.alloc(C * Dp);
+    grad.alloc(C * Dp);
+    lp.alloc(C);
+    std::vector<double> padded(C * Dp, 0.0);
+    for (size_t c = 0; c < C; ++c) std::memcpy(&padded[c * Dp], theta + c * D, sizeof(double) * D);
+    HIP_OK(hipMemcpyAsync(th.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    wn::InitParams Q{};
+    Q.num_chains = static_cast<int32_t>(C);
+    Q.dim = e->D;
+    Q.dim_padded = e->Dp;
+    Q.theta = th.p;
+    Q.model_params = e->model_params.p;
+    Q.scratch = e->arena.p;
+    Q.scratch_stride = e->arena_stride;
+    Q.data_x = e->data_x.p;
+    Q.data_y = e->data_y.p;
+    Q.num_obs = e->num_obs;
+    Q.data_stride = e->Dp;
+    Q.logp_out = lp.p;
+    Q.grad_out = grad.p;
+    const int grid = e->geo.mem ? e->grid : static_cast<int>(std::min<size_t>(C, static_cast<size_t>(e->num_cus) * 8));
+    wn::launch_eval(e->model, e->geo, grid, wn::transition_smem_bytes(e->geo.nw, 0, e->Dp), e->stream,
+                    e->cfg.fused_multiply_add != 0, Q);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpy2DAsync(grad_out, sizeof(double) * D, grad.p, sizeof(double) * Dp, sizeof(double) * D, C,
+                            hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(logp_out, lp.p, C * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+  });
+}
 
 int wn_engine_set_positions(wn_engine* e, const double* positions, WalnutpyError** err) {
   return guarded(err, [&] {

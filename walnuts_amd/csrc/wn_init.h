@@ -24,6 +24,14 @@ struct InitParams {
   double scale, smoothing;
   uint64_t pos_seed, step_seed;
   uint32_t pos_chain_offset, step_chain_offset;
+  // a data model's observations (Params::data_x ...)
+  const double* data_x;
+  const double* data_y;
+  int32_t num_obs;
+  int32_t data_stride;
+  // eval_kernel (wn_engine_eval): the model's log density [C] and gradient [C][Dp] at theta
+  double* logp_out;
+  double* grad_out;
 };
 
 template <class Model, int NW, int EPL>
@@ -35,6 +43,10 @@ __global__ __launch_bounds__(64 * NW) void init_kernel(const InitParams Q) {
   P.dim = Q.dim;
   P.dim_padded = Q.dim_padded;
   P.model_params = Q.model_params;
+  P.data_x = Q.data_x;
+  P.data_y = Q.data_y;
+  P.num_obs = Q.num_obs;
+  P.data_stride = Q.data_stride;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;
@@ -123,6 +135,96 @@ __global__ __launch_bounds__(64 * NW) void init_kernel(const InitParams Q) {
       if (t.tid == 0) Q.step_init[chain] = step;
     }
     if (t.tid == 0) Q.grad_evals[chain] += t.n_grad;
+  }
+}
+
+// wn_engine_eval: the model's log density and gradient at the caller's positions (Q.theta), in the engine's arithmetic
+// mode (FMA) -- the same expressions a transition evaluates, nothing else read or written.  Q.logp_out[C] and
+// Q.grad_out[C][Dp] (padding slots 0).  The device form of the reference's logp_grad(theta) -> (logp, grad).
+template <class Model, int NW, int EPL, bool FMA>
+__global__ __launch_bounds__(64 * NW) void eval_kernel(const InitParams Q) {
+  WN_DYN_SMEM(smem);
+  using T = TrajChip<Model, NW, EPL, false, FMA>;
+  Params P{};
+  P.num_chains = Q.num_chains;
+  P.dim = Q.dim;
+  P.dim_padded = Q.dim_padded;
+  P.model_params = Q.model_params;
+  P.data_x = Q.data_x;
+  P.data_y = Q.data_y;
+  P.num_obs = Q.num_obs;
+  P.data_stride = Q.data_stride;
+  WN_LDS double* base = (WN_LDS double*)smem;
+  WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
+  WN_LDS double* red = base + NW * kMetaDoubles;
+  WN_LDS double* bcast = red + kRedDoubles(NW);
+  T t(P, base, meta, red, bcast, nullptr);
+  for (int chain = blockIdx.x; chain < Q.num_chains; chain += gridDim.x) {
+    const long long row = static_cast<long long>(chain) * Q.dim_padded;
+    if (Model::kUsesParams) t.vload(Q.model_params, t.mp);
+    t.vload(Q.theta + row, t.th[0]);
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      t.rh[0][j] = 0.0;  // (energy_partials also forms a kinetic partial: of nothing here)
+      t.im[j] = 0.0;
+    }
+    double part = t.template model_eval<0>(), ke;
+    t.template energy_partials<0>(part, ke);
+    t.sum2(part, ke);
+    const double lp = Model::finish(part, t.aux, Q.dim);
+    double g[EPL];
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) g[j] = t.valid(j) ? t.template G<0>(j) : 0.0;
+    t.vstore(Q.grad_out + row, g);
+    if (t.tid == 0) Q.logp_out[chain] = lp;
+  }
+}
+
+// ... for the streaming backend (vectors in HBM, two coordinates per lane at a time)
+template <class Model, int NW, bool FMA>
+__global__ __launch_bounds__(64 * NW) void eval_kernel_mem(const InitParams Q) {
+  WN_DYN_SMEM(smem);
+  using T = TrajMem<Model, NW, FMA>;
+  Params P{};
+  P.num_chains = Q.num_chains;
+  P.dim = Q.dim;
+  P.dim_padded = Q.dim_padded;
+  P.model_params = Q.model_params;
+  WN_LDS double* base = (WN_LDS double*)smem;
+  WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
+  WN_LDS double* red = base + NW * kMetaDoubles;
+  WN_LDS double* bcast = red + kRedDoubles(NW);
+  T t(P, base, meta, red, bcast, Q.scratch + static_cast<long long>(blockIdx.x) * Q.scratch_stride);
+  constexpr int L = T::L;
+  const int tiles = Q.dim_padded / (2 * L);
+  for (int chain = blockIdx.x; chain < Q.num_chains; chain += gridDim.x) {
+    const long long row = static_cast<long long>(chain) * Q.dim_padded;
+    typename Model::Aux aux{};
+    if constexpr (T::kTwoPass) t.aux_of(Q.theta + row, aux);
+    double lp = 0.0, unused = 0.0;
+    for (int k = 0; k < tiles; ++k) {
+      const int o = t.pair_offset(k);
+      const v2f64 t0 = T::ld(Q.theta + row + o);
+      double th2[2] = {t0[0], t0[1]}, g2[2], mp2[2] = {1.0, 1.0};
+      if (Model::kUsesParams) {
+        const v2f64 p0 = T::ld(Q.model_params + o);
+        mp2[0] = p0[0];
+        mp2[1] = p0[1];
+      }
+      typename T::TileCx cx{o, Q.dim};
+      if constexpr (T::kTwoPass) {
+        double prev[2], next[2];
+        t.halo(Q.theta + row, o, t0, prev, next);
+        Model::stream_grad(cx, th2, prev, next, mp2, g2, aux);
+        Model::stream_logp(cx, th2, prev, next, mp2, aux, lp);
+      } else {
+        Model::eval(cx, th2, g2, mp2, aux, lp);
+      }
+      T::st(Q.grad_out + row + o, o < Q.dim ? g2[0] : 0.0, o + 1 < Q.dim ? g2[1] : 0.0);
+    }
+    t.sum2(lp, unused);
+    const double logp = Model::finish(lp, aux, Q.dim);
+    if (t.tid == 0) Q.logp_out[chain] = logp;
   }
 }
 

@@ -17,6 +17,10 @@ namespace wn {
 
 // streaming (num_params > 8192) kernels exist for element-wise gradients and for models that state their streaming form
 static constexpr bool kHasStreaming = WN_MODEL_TYPE::kElementwise || is_streamable<WN_MODEL_TYPE>::value;
+// a data model (kUsesData) runs one wavefront per chain: no kernels are built for wider register geometries
+static constexpr bool kUsesData = uses_data<WN_MODEL_TYPE>::value;
+static_assert(!(kUsesData && kHasStreaming), "a data model has no streaming form (wn_model_api.h)");
+static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }
 
 void WN_CAT(launch_transition_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem, hipStream_t stream,
                                                const Params& p) {
@@ -47,16 +51,18 @@ void WN_CAT(launch_transition_, WN_MODEL_TAG)(const Geometry& g, int grid, size_
 #define WN_LAUNCH_CHIP(NW, EPL, WARM, FMA) \
   hipLaunchKernelGGL((transition_kernel_chip<WN_MODEL_TYPE, NW, EPL, WARM, FMA>), dim3(grid), dim3(64 * NW), smem, stream, p)
 #define WN_X(NW, EPL)                           \
-  if (g.nw == NW && g.epl == EPL) {             \
-    if (p.warmup && p.fma)                      \
-      WN_LAUNCH_CHIP(NW, EPL, true, true);      \
-    else if (p.warmup)                          \
-      WN_LAUNCH_CHIP(NW, EPL, true, false);     \
-    else if (p.fma)                             \
-      WN_LAUNCH_CHIP(NW, EPL, false, true);     \
-    else                                        \
-      WN_LAUNCH_CHIP(NW, EPL, false, false);    \
-    return;                                     \
+  if constexpr (geometry_built(NW)) {           \
+    if (g.nw == NW && g.epl == EPL) {           \
+      if (p.warmup && p.fma)                    \
+        WN_LAUNCH_CHIP(NW, EPL, true, true);    \
+      else if (p.warmup)                        \
+        WN_LAUNCH_CHIP(NW, EPL, true, false);   \
+      else if (p.fma)                           \
+        WN_LAUNCH_CHIP(NW, EPL, false, true);   \
+      else                                      \
+        WN_LAUNCH_CHIP(NW, EPL, false, false);  \
+      return;                                   \
+    }                                           \
   }
   WN_FOR_EACH_GEOMETRY(WN_X)
 #undef WN_X
@@ -77,10 +83,45 @@ void WN_CAT(launch_init_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem
     }
     throw std::invalid_argument("this model has no streaming (large num_params) kernel");
   }
-#define WN_X(NW, EPL)                                                                                       \
-  if (g.nw == NW && g.epl == EPL) {                                                                         \
-    hipLaunchKernelGGL((init_kernel<WN_MODEL_TYPE, NW, EPL>), dim3(grid), dim3(64 * NW), smem, stream, q);  \
-    return;                                                                                                 \
+#define WN_X(NW, EPL)                                                                                         \
+  if constexpr (geometry_built(NW)) {                                                                         \
+    if (g.nw == NW && g.epl == EPL) {                                                                         \
+      hipLaunchKernelGGL((init_kernel<WN_MODEL_TYPE, NW, EPL>), dim3(grid), dim3(64 * NW), smem, stream, q);  \
+      return;                                                                                                 \
+    }                                                                                                         \
+  }
+  WN_FOR_EACH_GEOMETRY(WN_X)
+#undef WN_X
+  throw std::invalid_argument("no kernel for this geometry");
+}
+
+// wn_engine_eval: the model at positions the caller chose (eval_kernel / eval_kernel_mem, wn_init.h)
+void WN_CAT(launch_eval_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem, hipStream_t stream, bool fma,
+                                         const InitParams& q) {
+  if (g.mem) {
+    if constexpr (kHasStreaming) {
+#define WN_X(NW)                                                                                                 \
+  if (g.nw == NW) {                                                                                              \
+    if (fma)                                                                                                     \
+      hipLaunchKernelGGL((eval_kernel_mem<WN_MODEL_TYPE, NW, true>), dim3(grid), dim3(64 * NW), smem, stream, q);  \
+    else                                                                                                         \
+      hipLaunchKernelGGL((eval_kernel_mem<WN_MODEL_TYPE, NW, false>), dim3(grid), dim3(64 * NW), smem, stream, q); \
+    return;                                                                                                      \
+  }
+      WN_FOR_EACH_MEM_GEOMETRY(WN_X)
+#undef WN_X
+    }
+    throw std::invalid_argument("this model has no streaming (large num_params) kernel");
+  }
+#define WN_X(NW, EPL)                                                                                              \
+  if constexpr (geometry_built(NW)) {                                                                              \
+    if (g.nw == NW && g.epl == EPL) {                                                                              \
+      if (fma)                                                                                                     \
+        hipLaunchKernelGGL((eval_kernel<WN_MODEL_TYPE, NW, EPL, true>), dim3(grid), dim3(64 * NW), smem, stream, q);  \
+      else                                                                                                         \
+        hipLaunchKernelGGL((eval_kernel<WN_MODEL_TYPE, NW, EPL, false>), dim3(grid), dim3(64 * NW), smem, stream, q); \
+      return;                                                                                                      \
+    }                                                                                                              \
   }
   WN_FOR_EACH_GEOMETRY(WN_X)
 #undef WN_X
@@ -119,15 +160,17 @@ void WN_CAT(prepare_, WN_MODEL_TAG)(const Geometry& g, size_t smem) {
   if (e == hipSuccess)                                                                                    \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&transition_kernel_chip<WN_MODEL_TYPE, NW, EPL, WARM, FMA>), \
                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-#define WN_X(NW, EPL)                                                                                       \
-  if (g.nw == NW && g.epl == EPL) {                                                                         \
-    hipError_t e = hipSuccess;                                                                              \
-    WN_SET_SMEM(NW, EPL, true, true)                                                                        \
-    WN_SET_SMEM(NW, EPL, true, false)                                                                       \
-    WN_SET_SMEM(NW, EPL, false, true)                                                                       \
-    WN_SET_SMEM(NW, EPL, false, false)                                                                      \
-    if (e != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); \
-    return;                                                                                                 \
+#define WN_X(NW, EPL)                                                                                         \
+  if constexpr (geometry_built(NW)) {                                                                         \
+    if (g.nw == NW && g.epl == EPL) {                                                                         \
+      hipError_t e = hipSuccess;                                                                              \
+      WN_SET_SMEM(NW, EPL, true, true)                                                                        \
+      WN_SET_SMEM(NW, EPL, true, false)                                                                       \
+      WN_SET_SMEM(NW, EPL, false, true)                                                                       \
+      WN_SET_SMEM(NW, EPL, false, false)                                                                      \
+      if (e != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); \
+      return;                                                                                                 \
+    }                                                                                                         \
   }
   WN_FOR_EACH_GEOMETRY(WN_X)
 #undef WN_X
@@ -171,6 +214,15 @@ int WN_CAT(hold_tiles_, WN_MODEL_TAG)(int nw) {
 }
 void WN_CAT(host_params_, WN_MODEL_TAG)(double* p, int n) { call_host_params<WN_MODEL_TYPE>(p, n, 0); }
 void WN_CAT(validate_, WN_MODEL_TAG)(int n) { call_validate<WN_MODEL_TYPE>(n, 0); }
+template <class M>
+auto call_host_data(const double* x, const double* y, int n, int d, int) -> decltype(M::host_data(x, y, n, d), void()) {
+  M::host_data(x, y, n, d);
+}
+template <class M>
+void call_host_data(const double*, const double*, int, int, long) {}
+void WN_CAT(host_data_, WN_MODEL_TAG)(const double* x, const double* y, int n, int d) {
+  call_host_data<WN_MODEL_TYPE>(x, y, n, d, 0);
+}
 }  // namespace
 
 #define WN_STR2(x) #x
@@ -188,7 +240,10 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     &WN_CAT(host_params_, WN_MODEL_TAG),
     &WN_CAT(validate_, WN_MODEL_TAG),
     &WN_CAT(hold_tiles_, WN_MODEL_TAG),
-    mem_register_dim_limit<WN_MODEL_TYPE>()};
+    mem_register_dim_limit<WN_MODEL_TYPE>(),
+    kUsesData,
+    &WN_CAT(launch_eval_, WN_MODEL_TAG),
+    &WN_CAT(host_data_, WN_MODEL_TAG)};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

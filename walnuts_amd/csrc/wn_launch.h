@@ -182,6 +182,11 @@ struct ModelOps {
   int (*hold_tiles)(int nw);  // streaming kernels of nw wavefronts: tiles of the moving end held in registers (0: none)
   int register_dim_limit;     // the largest num_params the register kernels serve by default when the held streaming
                               // kernels exist (mem_register_dim_limit<Model>(), wn_traj.h)
+  bool uses_data;             // reads an observation block (kUsesData): one wavefront per chain, register kernels only
+  // the model's log density and gradient at given positions (eval_kernel, wn_init.h: wn_engine_eval)
+  void (*launch_eval)(const Geometry&, int grid, size_t smem, hipStream_t, bool fma, const InitParams&);
+  // data models: validate the observations before upload (x [num_obs][num_params] row-major, y [num_obs])
+  void (*host_data)(const double* x, const double* y, int num_obs, int num_params);
 };
 constexpr int kMaxModels = 64;
 inline const ModelOps** model_table() {
@@ -196,7 +201,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 8;
+constexpr int kModelAbiVersion = 9;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;
@@ -244,6 +249,9 @@ inline void launch_transition(int model, const Geometry& g, int grid, size_t sme
 }
 inline void launch_init(int model, const Geometry& g, int grid, size_t smem, hipStream_t s, const InitParams& q) {
   model_ops(model).launch_init(g, grid, smem, s, q);
+}
+inline void launch_eval(int model, const Geometry& g, int grid, size_t smem, hipStream_t s, bool fma, const InitParams& q) {
+  model_ops(model).launch_eval(g, grid, smem, s, fma, q);
 }
 // wavefronts per SIMD the register kernel of this model / geometry is compiled for (its VGPR budget)
 inline int waves_per_simd(int model, const Geometry& g) { return model_ops(model).waves_per_simd(g); }

@@ -53,6 +53,14 @@
 //     static constexpr int kPreferredElemsPerLane;
 //     // ... or, where the best width depends on the dimension, the same hint as a function (0 = the default policy there):
 //     static constexpr int preferred_elems_per_lane(int num_params);
+//
+//     // optional -- a model CONDITIONED ON DATA: the engine keeps a read-only observation block in HBM (x: num_obs rows
+//     // of num_params doubles, y: num_obs doubles; wn_engine_create_with_data / walnutpie_sample_device_data*), and
+//     // eval() reads it through the cx calls below.  A data model runs one wavefront per chain on the register kernels
+//     // (1 <= num_params <= 1024, any num_obs >= 1): it declares no streaming form, and wn_engine_create refuses other
+//     // geometries, a data model without data and data for a model without this member (`config` errors).
+//     static constexpr bool kUsesData = true;
+//     static void host_data(const double* x, const double* y, int num_obs, int num_params);  // optional checks (throw)
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -62,19 +70,31 @@
 //   cx.shift(v, prev, next)                   prev[j] = v at coordinate index(j) - 1, next[j] = v at index(j) + 1
 //                                             (0.0 beyond either end of the padded vector)
 //   cx.uniform_tab()                          tables for wnd::dexp / wnd::dlog of a wave-uniform argument
+//   cx.gather_tab()                           the same tables for a per-lane argument (every lane takes part)
 //   Cx::mad(a, b, c)                          a * b + c: one fused multiply-add when the engine was created with
 //                                             wn_config::fused_multiply_add, a rounded product plus an add otherwise
+// ... and, compiled in for data models only (kUsesData; one wavefront per chain, so Cx::L == 64):
+//   cx.num_obs()                              number of observations, wave-uniform
+//   cx.load_row(n, x)                         double x[EPL] = the lane's slots of row n of x: slot j holds column
+//                                             cx.index(j), zero beyond num_params (a row is laid out like theta and
+//                                             loads with the same 16-byte pair loads); n wave-uniform, 0 <= n < num_obs
+//   cx.obs_y(n)                               y[n] (0 <= n < num_obs)
+// The wavefront primitives of the platform layer (wave_sum_packed, lane_value, set_lane, uni, ...: wn_gfx950.h, with
+// the same association order under the CPU emulation) are available to eval(); models/glm.h uses them to reduce two
+// rows' dot products per butterfly.
 // Arithmetic: the library is compiled with -ffp-contract=off; what you write is what is evaluated (Cx::mad is the one
 // place where the engine's arithmetic mode shows), so a CPU restatement of the same expressions reproduces the device
 // bit for bit (that is how the parity tests work).
 //
 // Registration is a five-line translation unit, wn_kernels_<name>.hip, that the Makefile picks up by its name:
 //   #include "models/my_model.h"
-//   #define WN_MODEL_ID 4                 // 0-3 are taken (std_normal, diag_normal, funnel, rw1); < 64
+//   #define WN_MODEL_ID 6                 // 0-5 are taken (std_normal, diag_normal, funnel, rw1, linear_regression,
+//                                         //   logistic_regression); < 64
 //   #define WN_MODEL_TAG my_model         // wn_model_id("my_model") finds it at run time
 //   #define WN_MODEL_TYPE wn::MyModel
 //   #include "wn_kernels.inc"
-// models/rw1.h is a complete example (the reference's AR(1) density with a neighbour-coupled gradient).
+// models/rw1.h is a complete example (the reference's AR(1) density with a neighbour-coupled gradient); models/glm.h
+// one of a model conditioned on data (Bayesian linear and logistic regression).
 #pragma once
 
 #include "wn_devmath.h"

@@ -92,6 +92,12 @@ struct Params {
                           // previous launch's last transition yet (this launch's first prologue applies the observation);
                           // 2 = apply that observation and do nothing else (the engine's flush); 0 = nothing pending
   uint32_t* error_flags;  // OR of kErr* bits of every chain and transition since wn_engine_check last read (and cleared) it
+  // observations of a data model (wn_model_api.h, kUsesData; null / 0 otherwise), read-only and shared by every chain:
+  // data_x is num_obs rows of data_stride (= Dp) doubles, each laid out like a theta row and zero beyond num_params
+  const double* data_x;
+  const double* data_y;  // [num_obs]
+  int32_t num_obs;
+  int32_t data_stride;
 };
 
 enum : uint32_t {

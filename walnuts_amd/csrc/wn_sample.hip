@@ -782,8 +782,15 @@ struct ResidentRequest {  // walnutpie_sample_device_resident
   bool all_gather = false;  // multi-device: chains_out is an array of num_devices handles, every device gets the whole block
 };
 
+// a data model's observations (walnutpie_sample_device_data*): host pointers, copied by wn_engine_create_with_data
+struct SampleData {
+  const double* x;  // [num_obs][num_params]
+  const double* y;  // [num_obs]
+  int num_obs;
+};
+
 static int sample_device_impl(
-    bool reference_streams, const ResidentRequest* resident, const ShardCtx* shard,
+    bool reference_streams, const ResidentRequest* resident, const ShardCtx* shard, const SampleData* data,
     int model, const double* model_params, int num_params, const double* inits, size_t num_chains,
     unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
     int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
@@ -871,7 +878,12 @@ static int sample_device_impl(
     // started once the device allocations are done -- see below)
     std::unique_ptr<Prefault> populate;
     EngineGuard guard;
-    WN_CALL(wn_engine_create(&guard.e, model, num_params, model_params, num_chains, &cfg, &call_err_));
+    if (data != nullptr) {
+      WN_CALL(wn_engine_create_with_data(&guard.e, model, num_params, model_params, data->x, data->y, data->num_obs,
+                                         num_chains, &cfg, &call_err_));
+    } else {
+      WN_CALL(wn_engine_create(&guard.e, model, num_params, model_params, num_chains, &cfg, &call_err_));
+    }
     wn_engine* e = guard.e;
     const size_t D = static_cast<size_t>(num_params);
     timer.mark("engine created");
@@ -1202,10 +1214,10 @@ extern "C" int walnutpie_sample_bridgestan(const char*, const char*, STREAM_CALL
 extern "C" char walnutpie_separator_char(void) { return '\x1C'; }  // walnutpy.cpp:224-225 (ASCII file separator)
 
 extern "C" int walnutpie_sample_device(WN_SAMPLE_PARAMS) {
-  return sample_device_impl(false, nullptr, nullptr, WN_SAMPLE_ARGS);
+  return sample_device_impl(false, nullptr, nullptr, nullptr, WN_SAMPLE_ARGS);
 }
 extern "C" int walnutpie_sample_device_reference_streams(WN_SAMPLE_PARAMS) {
-  return sample_device_impl(true, nullptr, nullptr, WN_SAMPLE_ARGS);
+  return sample_device_impl(true, nullptr, nullptr, nullptr, WN_SAMPLE_ARGS);
 }
 #undef WN_SAMPLE_PARAMS
 #define WN_SAMPLE_PARAMS_NOERR                                                                                    \
@@ -1222,8 +1234,31 @@ extern "C" int walnutpie_sample_device_reference_streams(WN_SAMPLE_PARAMS) {
 extern "C" int walnutpie_sample_device_resident(WN_SAMPLE_PARAMS_NOERR, int thin, wn_chains** chains_out,
                                                 WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out};
-  return sample_device_impl(false, &req, nullptr, WN_SAMPLE_ARGS);
+  return sample_device_impl(false, &req, nullptr, nullptr, WN_SAMPLE_ARGS);
 }
+// the same two calls for a model conditioned on data (x, y, num_obs after num_params)
+#define WN_DATA_SAMPLE_PARAMS_NOERR                                                                               \
+  int model, const double *model_params, int num_params, const double *x, const double *y, int num_obs,          \
+      const double *inits, size_t num_chains, unsigned int seed, unsigned int id, double init_radius,             \
+      const double *init_inv_metric, int min_warmup_iter, int max_warmup_iter, int min_sampling_iter,            \
+      int max_sampling_iter, int max_trajectory_doublings, int max_step_halvings, int min_micro_steps,           \
+      double max_hamiltonian_error, double step_size_converge_tol, double mass_converge_tol,                      \
+      double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,                          \
+      double max_macro_steps_target, double step_size_init, double step_accept_rate_target,                      \
+      double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,                      \
+      double step_stabilization, double step_learn_rate_decay, bool save_warmup, double *out, size_t out_size,  \
+      int *final_lengths, double *stepsize_out, double *inv_metric_out, int refresh, PRINT_CALLBACK print
+extern "C" int walnutpie_sample_device_data(WN_DATA_SAMPLE_PARAMS_NOERR, WalnutpyError** err) {
+  const SampleData data{x, y, num_obs};
+  return sample_device_impl(false, nullptr, nullptr, &data, WN_SAMPLE_ARGS);
+}
+extern "C" int walnutpie_sample_device_data_resident(WN_DATA_SAMPLE_PARAMS_NOERR, int thin, wn_chains** chains_out,
+                                                     WalnutpyError** err) {
+  const ResidentRequest req{thin, chains_out};
+  const SampleData data{x, y, num_obs};
+  return sample_device_impl(false, &req, nullptr, &data, WN_SAMPLE_ARGS);
+}
+#undef WN_DATA_SAMPLE_PARAMS_NOERR
 
 // walnutpie_sample_device over several devices of the node: one host thread, engine and stream per entry of `devices`
 // (an ordinal may repeat: two shards on one device overlap each other's launch tails), contiguous shards of the global
@@ -1296,7 +1331,7 @@ static int sample_multi_impl(const ResidentRequest* resident, WN_SAMPLE_PARAMS_N
         double* metric_out_s = inv_metric_out == nullptr ? nullptr : inv_metric_out + ctx.chain_begin * D;
         const ResidentRequest shard_req{resident != nullptr ? resident->thin : 0, &shard_chains[static_cast<size_t>(s)]};
         rcs[s] = sample_device_impl(
-            false, resident != nullptr ? &shard_req : nullptr, &ctx, model, model_params, num_params, inits_s, count, seed, id, init_radius, metric_s,
+            false, resident != nullptr ? &shard_req : nullptr, &ctx, nullptr, model, model_params, num_params, inits_s, count, seed, id, init_radius, metric_s,
             min_warmup_iter, max_warmup_iter, min_sampling_iter, max_sampling_iter, max_trajectory_doublings,
             max_step_halvings, min_micro_steps, max_hamiltonian_error, step_size_converge_tol, mass_converge_tol,
             rhat_converge_tol, mass_init_count, mass_additive_smoothing, max_macro_steps_target, step_size_init,

@@ -961,6 +961,12 @@ template <class M, class = void>
 struct is_streamable : std::false_type {};
 template <class M>
 struct is_streamable<M, std::enable_if_t<M::kStreamable>> : std::true_type {};
+// A data model (wn_model_api.h: kUsesData) reads the engine's observation block through cx.num_obs() / load_row() /
+// obs_y(); models without the member read nothing beyond theta and their parameter vector.
+template <class M, class = void>
+struct uses_data : std::false_type {};
+template <class M>
+struct uses_data<M, std::enable_if_t<M::kUsesData>> : std::true_type {};
 template <class M, bool Elementwise = M::kElementwise>
 struct StreamTraits {
   static constexpr bool kTwoPass = false, kHasSums = false, kHalo = false;

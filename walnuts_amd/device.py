@@ -136,6 +136,7 @@ def walnuts_device(
     all_gather: bool = False,
     lib_path: Optional[str] = None,
     print_callback=None,
+    data=None,
 ):
     """The device-model sibling of the reference's ``walnuts_pyfunc`` (pyfunc.py:45-286): same keywords, same result
     (a list of per-chain draw arrays carrying ``.warmup``).
@@ -153,8 +154,17 @@ def walnuts_device(
     ``keep_on_device=True`` (walnutpie_sample_device_multi_resident) every shard keeps its draws on its own device and
     the blocks are gathered on ``devices[0]`` by peer-to-peer copies at the end: one ``MarkovChains`` handle there;
     with ``all_gather=True`` as well (walnutpie_sample_device_multi_allgather) EVERY listed device ends with the whole
-    block -- the call returns ``(results, [chains on devices[0], chains on devices[1], ...])``."""
+    block -- the call returns ``(results, [chains on devices[0], chains on devices[1], ...])``.
+
+    ``data=(x, y)`` (walnutpie_sample_device_data / _data_resident): the observations of a model conditioned on data
+    (``MODEL_LINEAR_REGRESSION``, ``MODEL_LOGISTIC_REGRESSION`` or a model of your own that declares ``kUsesData``),
+    ``x`` of shape (num_obs, num_params) and ``y`` of shape (num_obs,); copied to the device once.  One device only:
+    not with ``devices`` or ``reference_streams``."""
     lib = _ffi.load_library(lib_path)
+    if data is not None and devices is not None:
+        raise ValueError("data is not available with devices (data models run on one device)")
+    if data is not None and reference_streams:
+        raise ValueError("data is not available with reference_streams")
     if devices is not None and reference_streams:
         raise ValueError("devices is not available with reference_streams")
     if keep_on_device and reference_streams:
@@ -178,6 +188,12 @@ def walnuts_device(
         raise ValueError("At least one of num_params or inits must be specified")
     if seed is None:
         seed = int(np.random.randint(0, 2**32 - 1, dtype=np.uint32))
+    data_args = ()
+    if data is not None:
+        from .engine import _data_arrays
+
+        x, y = _data_arrays(data, num_params)
+        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), y.size)
     mp = None if model_params is None else np.ascontiguousarray(np.asarray(model_params, dtype=np.float64))
     if mp is not None and mp.size != num_params:
         raise ValueError("model_params must have num_params entries")
@@ -211,6 +227,8 @@ def walnuts_device(
     if keep_on_device:
         entry = lib.walnutpie_sample_device_resident
         tail = (refresh, cb, thin, C.byref(chains_handle), C.byref(err))
+    if data is not None:
+        entry = lib.walnutpie_sample_device_data_resident if keep_on_device else lib.walnutpie_sample_device_data
     if devices is not None:
         dev = (C.c_int * len(devices))(*[int(d) for d in devices])
         entry = lib.walnutpie_sample_device_multi
@@ -229,7 +247,7 @@ def walnuts_device(
     timing = os.environ.get("WALNUTS_AMD_TIMING") is not None   # the C side prints its phases under the same switch
     t_call = time.perf_counter()
     rc = entry(
-        model, None if mp is None else mp.ctypes.data_as(dp), num_params,
+        model, None if mp is None else mp.ctypes.data_as(dp), num_params, *data_args,
         None if inits is None else inits.ctypes.data_as(dp), num_chains, seed, id, init_radius,
         None if inv_metric_init is None else inv_metric_init.ctypes.data_as(dp), min_warmup_iter, max_warmup_iter,
         min_sampling_iter, max_sampling_iter, max_trajectory_doublings, max_step_halvings, min_micro_steps,

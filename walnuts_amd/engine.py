@@ -15,6 +15,8 @@ import numpy as np
 from . import _ffi
 
 MODEL_STD_NORMAL, MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_RW1 = 0, 1, 2, 3
+# models conditioned on data (walnuts_amd/csrc/models/glm.h): params = the prior variances, data = (x, y)
+MODEL_LINEAR_REGRESSION, MODEL_LOGISTIC_REGRESSION = 4, 5
 _dp = _ffi._dp
 
 
@@ -45,9 +47,27 @@ def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _data_arrays(data, num_params: int):
+    """(x, y) of a data model as contiguous float64 arrays: x (num_obs, num_params), y (num_obs,)."""
+    try:
+        x, y = data
+    except (TypeError, ValueError):
+        raise ValueError("data must be a pair (x, y)") from None
+    x, y = _f64(x), _f64(y)
+    if x.ndim != 2 or x.shape[1] != num_params:
+        raise ValueError(f"data x must have shape (num_obs, {num_params}), got {x.shape}")
+    if y.ndim != 1 or y.shape[0] != x.shape[0]:
+        raise ValueError(f"data y must have shape ({x.shape[0]},), got {y.shape}")
+    if x.shape[0] < 1:
+        raise ValueError("data needs at least one observation")
+    return x, y
+
+
 class DeviceEngine:
     def __init__(self, model: int, dim: int, num_chains: int, cfg: Optional[_ffi.Config] = None,
-                 params: Optional[np.ndarray] = None, lib_path: Optional[str] = None):
+                 params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None):
+        """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
+        (num_obs, dim) and y of shape (num_obs,); copied to the device once."""
         self.lib = _ffi.load_library(lib_path)
         self.cfg = cfg if cfg is not None else default_config(lib_path)
         self.C, self.D = int(num_chains), int(dim)
@@ -55,8 +75,14 @@ class DeviceEngine:
         if p is not None and p.size != dim:
             raise ValueError("model params must have num_params entries")
         h, err = C.c_void_p(), C.c_void_p()
-        rc = self.lib.wn_engine_create(C.byref(h), model, dim, None if p is None else p.ctypes.data_as(_dp),
-                                       num_chains, C.byref(self.cfg), C.byref(err))
+        pp = None if p is None else p.ctypes.data_as(_dp)
+        if data is None:
+            rc = self.lib.wn_engine_create(C.byref(h), model, dim, pp, num_chains, C.byref(self.cfg), C.byref(err))
+        else:
+            x, y = _data_arrays(data, self.D)
+            rc = self.lib.wn_engine_create_with_data(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
+                                                     y.ctypes.data_as(_dp), y.size, num_chains, C.byref(self.cfg),
+                                                     C.byref(err))
         _ffi.check(self.lib, rc, err)
         self.h = h
 
@@ -142,6 +168,15 @@ class DeviceEngine:
     def check(self):
         """Raise if any chain's last transition could not complete on the device."""
         self._call(self.lib.wn_engine_check)
+
+    def logp_grad(self, theta):
+        """The model's (log density [C], gradient [C, D]) at positions theta [C, D] (wn_engine_eval), in the engine's
+        arithmetic mode; no chain state is read or changed."""
+        th = _f64(theta).reshape(self.C, self.D)
+        lp = np.empty(self.C)
+        g = np.empty((self.C, self.D))
+        self._call(self.lib.wn_engine_eval, th.ctypes.data_as(_dp), lp.ctypes.data_as(_dp), g.ctypes.data_as(_dp))
+        return lp, g
 
     # ---- state
     def _get(self, fn, shape, dtype=np.float64, ptr=_dp):
