@@ -242,3 +242,79 @@ def test_pinned_ring_path_of_the_draw_sink(sim, monkeypatch):
         _run(sim, max_warmup_iter=50, min_warmup_iter=50, refresh=1, print_callback=on_print)
     again = _run(sim, num_chains=5)
     assert all(np.array_equal(np.asarray(a), np.asarray(b)) for a, b in zip(whole, again))
+
+
+# one invalid value per checked argument (everything else valid) and the config error it must name: -1.0 is invalid
+# for every double argument, so an argument that reached another's place would be reported under that one's name
+_INVALID = [(name, {name: -1.0}, msg) for name, msg in (
+    ("init_radius", "init_scale must be finite and > 0"),
+    ("max_hamiltonian_error", "max_hamiltonian_error must be finite and > 0"),
+    ("step_size_converge_tol", "step_size_converge_tol must be finite and > 0"),
+    ("mass_converge_tol", "mass_converge_tol must be finite and > 0"),
+    ("rhat_converge_tol", "rhat_convergence_tol must be finite and > 1"),
+    ("mass_init_count", "mass_init_count must be finite and > 0"),
+    ("mass_additive_smoothing", "mass_additive_smoothing must be finite and > 0"),
+    ("max_macro_steps_target", "max_macro_steps_target must be finite and > 0"),
+    ("step_size_init", "step size must be finite and > 0"),
+    ("step_accept_rate_target", "step_accept_rate_target must be in (0, 1)"),
+    ("step_learning_rate", "step_learning_rate must be finite and > 0"),
+    ("step_gradient_decay", "step_gradient_decay must be in (0, 1)"),
+    ("step_sq_gradient_decay", "step_sq_gradient_decay must be in (0, 1)"),
+    ("step_stabilization", "step_stabilization must be finite and > 0"),
+    ("step_learn_rate_decay", "step_learn_rate_decay must be in (0, 1)"),
+)] + [
+    ("refresh", dict(refresh=-1), "refresh must be non-negative, was -1"),
+    ("min_micro_steps", dict(min_micro_steps=0), "min_micro_steps must be in {1, 2, ... }"),
+    ("min_warmup_iter", dict(min_warmup_iter=5), "min_iter cannot be greater than than max_iter"),
+    ("min_sampling_iter", dict(min_sampling_iter=8), "min_iter must be <= max_iter"),
+]
+
+
+@pytest.mark.timeout(900)
+def test_every_entry_point_routes_every_checked_argument(sim):
+    """Every entry family of walnutpie_sample_device* reports an invalid argument under that argument's own name: the
+    argument list reaches the checks unchanged, whichever entry point it came through."""
+    x = np.random.default_rng(1).normal(size=(8, 5))
+    data = dict(model_params=np.ones(5), data=(x, x @ np.linspace(-1.0, 1.0, 5)))
+    families = {
+        "plain": {},
+        "reference_streams": dict(reference_streams=True),
+        "resident": dict(keep_on_device=True, thin=2),
+        "data": data,
+        "data_resident": dict(keep_on_device=True, thin=2, **data),
+        "multi": dict(devices=[0, 0]),
+        "multi_resident": dict(devices=[0, 0], keep_on_device=True, thin=2),
+        "multi_allgather": dict(devices=[0, 0], keep_on_device=True, thin=2, all_gather=True),
+    }
+    for family, kw in families.items():
+        model = wa.MODEL_LINEAR_REGRESSION if "data" in kw else wa.MODEL_STD_NORMAL
+        for name, bad, msg in _INVALID:
+            with pytest.raises(ValueError) as info:
+                wa.walnuts_device(model, **{**dict(num_params=5, num_chains=3, seed=11, min_warmup_iter=4,
+                                                   max_warmup_iter=4, min_sampling_iter=7, max_sampling_iter=7,
+                                                   save_warmup=True, lib_path=sim, refresh=0), **kw, **bad})
+            assert str(info.value) == msg, (family, name, str(info.value))
+
+
+@pytest.mark.timeout(900)
+def test_multi_device_call_equals_the_single_engine_call_at_non_default_tuning(sim):
+    """walnutpie_sample_device_multi passes every tuning argument to every shard as the one-engine call uses it: with
+    each trajectory and adaptation argument at a distinct non-default value, two and three shards produce the same
+    draws, warmup draws, step sizes and inverse metrics bit for bit."""
+    kw = dict(num_chains=5, min_warmup_iter=9, max_warmup_iter=9, min_sampling_iter=6, max_sampling_iter=6,
+              init_radius=1.5, max_trajectory_doublings=4, max_step_halvings=3, min_micro_steps=2,
+              max_hamiltonian_error=0.37, step_size_converge_tol=0.2, mass_converge_tol=0.9, rhat_converge_tol=1.02,
+              mass_init_count=3.5, mass_additive_smoothing=2e-5, max_macro_steps_target=12.0, step_size_init=0.8,
+              step_accept_rate_target=0.75, step_learning_rate=0.07, step_gradient_decay=0.85,
+              step_sq_gradient_decay=0.93, step_stabilization=2e-4, step_learn_rate_decay=0.6)
+    whole = _run(sim, **kw)
+    default = _run(sim, num_chains=5, min_warmup_iter=9, max_warmup_iter=9, min_sampling_iter=6, max_sampling_iter=6)
+    assert not np.array_equal(np.asarray(whole[0]), np.asarray(default[0]))   # the tuning reached the sampler
+    for devices in ([0, 0], [0, 0, 0]):
+        other = _run(sim, devices=devices, **kw)
+        assert len(other) == 5
+        for a, b in zip(whole, other):
+            assert np.array_equal(np.asarray(a), np.asarray(b)), devices
+            assert np.array_equal(a.warmup.warmup_draws, b.warmup.warmup_draws), devices
+            assert a.warmup.stepsize == b.warmup.stepsize, devices
+            assert np.array_equal(a.warmup.inv_metric, b.warmup.inv_metric), devices

@@ -16,6 +16,7 @@
 // (walnutpy.cpp:82) instead of mt19937_64.
 #include "wn_hip.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <future>
 #include <iomanip>
 #include <memory>
 #include <random>
@@ -32,6 +34,7 @@
 #include <condition_variable>
 #include <deque>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <string>
 #include <vector>
@@ -671,14 +674,17 @@ struct PhaseTimer {
 
 constexpr int kMaxFusedTransitions = 8;  // transitions per launch between two looks of a controller
 
-// ---- several devices behind one call (walnutpie_sample_device_multi) ------------------------------------------------
+namespace {
+
+// ---- the controllers over the chains of one call, on one device or several ----------------------------------------
 // The chains shard embarrassingly (adapt.hpp:257-258: nothing is pooled per transition): shard s is a contiguous block
 // of GLOBAL chain ids on devices[s], driven by its own host thread, engine and stream, and writes its own slice of the
 // caller's out[C][T][D] -- no exchange on the data path.  What the shards share is what the reference's controller
 // threads look at: the warmup spread (adapt.hpp:193-221) and R-hat of the log density (sampler.hpp:139-145), each
 // reduced in the two stages the engine exposes (wn_engine_warmup_sums / _warmup_max_rel, wn_engine_lp_sums / _lp_sq_dev)
 // with a rendezvous of the shard threads in between, so that every shard takes the same stopping decision at the same
-// iteration.
+// iteration.  A one-device call is the one-shard case: every reduction starts from shard 0's value, so one shard
+// reproduces wn_engine_warmup_spread and wn_engine_rhat bit for bit.
 struct ShardAborted {};  // another shard failed: leave quietly, the wrapper reports that shard's error
 class Coordinator {
  public:
@@ -691,55 +697,41 @@ class Coordinator {
     if (arrived_ >= n_ && n_ > 0) release();
     cv_.notify_all();
   }
-  bool failed() const { return failed_; }
   // adapt.hpp:193-221 over ALL shards' chains
   bool warmup_converged(int shard, wn_engine* e, size_t total_chains, double step_tol, double mass_tol) {
-    double* mine = slot(shard);
-    WN_CALL(wn_engine_warmup_sums(e, mine, mine + 1, &call_err_));
-    rendezvous();
-    std::vector<double> total(D_ + 1, 0.0);
-    for (int s = 0; s < shards(); ++s)
-      for (size_t i = 0; i <= D_; ++i) total[i] += slot(s)[i];  // (every shard adds in the same order: same total)
-    rendezvous();  // everyone has read the sums before the slots are reused
-    double rel_step = 0, rel_mass = 0;
-    WN_CALL(wn_engine_warmup_max_rel(e, total[0], total.data() + 1, total_chains, &rel_step, &rel_mass, &call_err_));
-    mine[0] = rel_step;
-    mine[1] = rel_mass;
-    rendezvous();
-    double ms = 0, mm = 0;
-    for (int s = 0; s < shards(); ++s) {
-      ms = std::max(ms, slot(s)[0]);
-      mm = std::max(mm, slot(s)[1]);
-    }
-    rendezvous();
-    return mm <= mass_tol && ms <= step_tol;
+    std::vector<double> sums(D_ + 1);  // sum of log step sizes, column sums of log masses
+    WN_CALL(wn_engine_warmup_sums(e, sums.data(), sums.data() + 1, &call_err_));
+    all_reduce(shard, sums.data(), D_ + 1, [](double x, double y) { return x + y; });
+    double rel[2];  // largest relative distances: step, mass
+    WN_CALL(wn_engine_warmup_max_rel(e, sums[0], sums.data() + 1, total_chains, &rel[0], &rel[1], &call_err_));
+    all_reduce(shard, rel, 2, [](double x, double y) { return std::max(x, y); });
+    return rel[1] <= mass_tol && rel[0] <= step_tol;
   }
   // sampler.hpp:139-145 over ALL shards' chains
   double rhat(int shard, wn_engine* e) {
-    double* mine = slot(shard);
-    WN_CALL(wn_engine_lp_sums(e, mine, &call_err_));  // sum of means, sum of sample variances, chains
-    rendezvous();
-    double s0 = 0, s1 = 0, s2 = 0;
-    for (int s = 0; s < shards(); ++s) {
-      s0 += slot(s)[0];
-      s1 += slot(s)[1];
-      s2 += slot(s)[2];
-    }
-    rendezvous();
+    const auto sum = [](double x, double y) { return x + y; };
+    double s[3];  // sum of means, sum of sample variances, chains
+    WN_CALL(wn_engine_lp_sums(e, s, &call_err_));
+    all_reduce(shard, s, 3, sum);
     double q = 0;
-    WN_CALL(wn_engine_lp_sq_dev(e, s0 / s2, &q, &call_err_));
-    mine[0] = q;
-    rendezvous();
-    double qq = 0;
-    for (int s = 0; s < shards(); ++s) qq += slot(s)[0];
-    rendezvous();
-    const double variance_of_means = qq / (s2 - 1);  // util.hpp:401-404
-    const double mean_of_variances = s1 / s2;
+    WN_CALL(wn_engine_lp_sq_dev(e, s[0] / s[2], &q, &call_err_));
+    all_reduce(shard, &q, 1, sum);
+    const double variance_of_means = q / (s[2] - 1);  // util.hpp:401-404
+    const double mean_of_variances = s[1] / s[2];
     return std::sqrt(1 + variance_of_means / mean_of_variances);  // sampler.hpp:145
   }
 
  private:
-  int shards() const { return total_shards_; }
+  // v[0, n) of every shard combined by `op`, from shard 0's value on in shard order: every shard gets the same result
+  template <class Op>
+  void all_reduce(int shard, double* v, size_t n, Op op) {
+    std::copy(v, v + n, slot(shard));
+    rendezvous();
+    std::copy(slot(0), slot(0) + n, v);
+    for (int s = 1; s < total_shards_; ++s)
+      for (size_t i = 0; i < n; ++i) v[i] = op(v[i], slot(s)[i]);
+    rendezvous();  // everyone has read the slots before they are reused
+  }
   double* slot(int s) { return slots_.data() + static_cast<size_t>(s) * (D_ + 4); }
   void release() {
     arrived_ = 0;
@@ -767,304 +759,279 @@ class Coordinator {
   unsigned long generation_ = 0;
   std::atomic<bool> failed_{false};
 };
-struct ShardCtx {
-  int shard = 0, device = 0;
-  size_t chain_begin = 0, total_chains = 0;
-  Coordinator* coord = nullptr;
-  const InterruptGuard* interrupt = nullptr;  // the call's one SIGINT guard
-  int* lengths_warmup = nullptr;              // final_lengths slices of this shard
-  int* lengths_sampling = nullptr;
+
+// The exception in flight as the C API's error (errors.hpp): `config` for an invalid argument, `interrupt` with an empty
+// message for Ctrl-C, and none for a shard that stopped because another one failed (that one holds the call's error).
+int report_exception(WalnutpyError** err) {
+  const auto set = [err](const char* msg, WalnutpyErrorType type) {
+    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(msg, type));
+  };
+  try {
+    throw;
+  } catch (const ShardAborted&) {
+    if (err) *err = nullptr;
+  } catch (const InterruptException&) {
+    set("", interrupt);
+  } catch (const std::invalid_argument& ex) {
+    set(ex.what(), config);
+  } catch (const std::exception& ex) {
+    set(ex.what(), generic);
+  } catch (...) {
+    set("Unknown error", generic);
+  }
+  return -1;
+}
+
+// ---- the arguments --------------------------------------------------------------------------------------------------
+// The arguments from `inits` to `print` that every walnutpie_sample_device* entry point takes (include/walnuts_hip.h),
+// written down once: the entry points' parameter lists, SampleArgs and its initialisation are generated from this list.
+#define WN_SAMPLE_ARG_LIST(X)                                                                                              \
+  X(const double*, inits) X(size_t, num_chains) X(unsigned int, seed) X(unsigned int, id) X(double, init_radius)      \
+  X(const double*, init_inv_metric) X(int, min_warmup_iter) X(int, max_warmup_iter) X(int, min_sampling_iter)          \
+  X(int, max_sampling_iter) X(int, max_trajectory_doublings) X(int, max_step_halvings) X(int, min_micro_steps)         \
+  X(double, max_hamiltonian_error) X(double, step_size_converge_tol) X(double, mass_converge_tol)                      \
+  X(double, rhat_converge_tol) X(double, mass_init_count) X(double, mass_additive_smoothing)                           \
+  X(double, max_macro_steps_target) X(double, step_size_init) X(double, step_accept_rate_target)                       \
+  X(double, step_learning_rate) X(double, step_gradient_decay) X(double, step_sq_gradient_decay)                       \
+  X(double, step_stabilization) X(double, step_learn_rate_decay) X(bool, save_warmup) X(double*, out)                  \
+  X(size_t, out_size) X(int*, final_lengths) X(double*, stepsize_out) X(double*, inv_metric_out) X(int, refresh)       \
+  X(PRINT_CALLBACK, print)
+#define WN_FIELD(type, name) type name;
+#define WN_PARAM(type, name) type name,
+#define WN_NAME(type, name) name,
+struct SampleArgs {
+  WN_SAMPLE_ARG_LIST(WN_FIELD)
 };
 
-struct ResidentRequest {  // walnutpie_sample_device_resident
+struct Model {  // the arguments in front of `inits`
+  int id;
+  const double* params;
+  int num_params;
+};
+
+// ... and the inputs of the entry points' modes
+struct ResidentRequest {  // walnutpie_sample_device*_resident, _multi_allgather
   int thin;
   wn_chains** chains_out;
   bool all_gather = false;  // multi-device: chains_out is an array of num_devices handles, every device gets the whole block
 };
-
 // a data model's observations (walnutpie_sample_device_data*): host pointers, copied by wn_engine_create_with_data
 struct SampleData {
   const double* x;  // [num_obs][num_params]
   const double* y;  // [num_obs]
   int num_obs;
 };
+struct Mode {
+  bool reference_streams = false;            // walnutpie_sample_device_reference_streams
+  const ResidentRequest* resident = nullptr;
+  const SampleData* data = nullptr;
+};
 
-static int sample_device_impl(
-    bool reference_streams, const ResidentRequest* resident, const ShardCtx* shard, const SampleData* data,
-    int model, const double* model_params, int num_params, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    WalnutpyError** err) {
-  try {
-    // walnutpy.cpp:151-160
-    if (refresh < 0) {
-      std::stringstream msg;
-      msg << "refresh must be non-negative, was " << refresh;
-      throw std::invalid_argument(msg.str());
-    }
-    if (num_params < 1) throw std::invalid_argument("num_params must be in {1, 2, ... }");
-    if (max_sampling_iter < 0 || max_warmup_iter < 0) throw std::invalid_argument("iteration counts must be >= 0");
-    const size_t warm_rows = save_warmup ? static_cast<size_t>(max_warmup_iter) : 0;
-    size_t samp_rows = static_cast<size_t>(max_sampling_iter);  // sampling rows per chain in the caller's buffer
-    if (resident != nullptr) {
-      if (resident->thin < 0) throw std::invalid_argument("thin must be non-negative");
-      if (resident->chains_out == nullptr) throw std::invalid_argument("chains_out must not be null");
-      if (max_sampling_iter < 1) throw std::invalid_argument("resident draws need max_sampling_iter >= 1");
-      *resident->chains_out = nullptr;
-      const size_t t = static_cast<size_t>(resident->thin);
-      samp_rows = t == 0 ? 0 : (static_cast<size_t>(max_sampling_iter) + t - 1) / t;
-    }
-    const size_t rows = samp_rows + warm_rows;
-    if (rows > 0 && out == nullptr) throw std::invalid_argument("out must not be null");
-    const size_t draws_offset = static_cast<size_t>(num_params) * rows;
-    // (a shard of walnutpie_sample_device_multi sees its own slice of a buffer the wrapper has checked as a whole)
-    const size_t total_chains = shard != nullptr ? shard->total_chains : num_chains;
-    const size_t chain_begin = shard != nullptr ? shard->chain_begin : 0;
-    if (shard == nullptr && out_size < num_chains * draws_offset) {
-      std::stringstream ss;
-      ss << "Output buffer too small. Expected at least " << num_chains << " chains of " << draws_offset
-         << " doubles, got " << out_size;
-      throw std::runtime_error(ss.str());
-    }
-    // WarmupConfigBuilder / SamplingConfigBuilder validation (config.hpp:656-850, 978-1059)
-    if (static_cast<size_t>(min_warmup_iter) > static_cast<size_t>(max_warmup_iter))
-      throw std::invalid_argument("min_iter cannot be greater than than max_iter");
-    finite_positive(step_size_converge_tol, "step_size_converge_tol");
-    finite_positive(mass_converge_tol, "mass_converge_tol");
-    finite_positive(mass_init_count, "mass_init_count");
-    finite_positive(mass_additive_smoothing, "mass_additive_smoothing");
-    finite_positive(max_macro_steps_target, "max_macro_steps_target");
-    probability(step_accept_rate_target, "step_accept_rate_target");
-    finite_positive(step_learning_rate, "step_learning_rate");
-    probability(step_gradient_decay, "step_gradient_decay");
-    probability(step_sq_gradient_decay, "step_sq_gradient_decay");
-    finite_positive(step_stabilization, "step_stabilization");
-    probability(step_learn_rate_decay, "step_learn_rate_decay");
-    if (static_cast<size_t>(min_sampling_iter) > static_cast<size_t>(max_sampling_iter))
-      throw std::invalid_argument("min_iter must be <= max_iter");
-    if (!(std::isfinite(rhat_converge_tol) && rhat_converge_tol > 1))
-      throw std::invalid_argument("rhat_convergence_tol must be finite and > 1");
-    finite_positive(max_hamiltonian_error, "max_hamiltonian_error");
-    if (min_micro_steps < 1) throw std::invalid_argument("min_micro_steps must be in {1, 2, ... }");
-    finite_positive(step_size_init, "step size");  // config.hpp:222
+// ---- validation, once per call, before any engine exists ------------------------------------------------------------
+struct Plan {
+  size_t warm_rows, rows;  // rows per chain of the caller's buffer: saved warmup rows; all of them
+  wn_config cfg;
+};
+Plan validate(const Model& m, const SampleArgs& a, const Mode& mode) {
+  // walnutpy.cpp:151-160
+  if (a.refresh < 0) {
+    std::stringstream msg;
+    msg << "refresh must be non-negative, was " << a.refresh;
+    throw std::invalid_argument(msg.str());
+  }
+  if (m.num_params < 1) throw std::invalid_argument("num_params must be in {1, 2, ... }");
+  if (a.max_sampling_iter < 0 || a.max_warmup_iter < 0) throw std::invalid_argument("iteration counts must be >= 0");
+  Plan p;
+  p.warm_rows = a.save_warmup ? static_cast<size_t>(a.max_warmup_iter) : 0;
+  size_t samp_rows = static_cast<size_t>(a.max_sampling_iter);
+  if (const ResidentRequest* r = mode.resident) {  // (the caller's buffer takes only every thin-th sampling draw)
+    if (r->thin < 0) throw std::invalid_argument("thin must be non-negative");
+    if (r->chains_out == nullptr) throw std::invalid_argument("chains_out must not be null");
+    if (a.max_sampling_iter < 1) throw std::invalid_argument("resident draws need max_sampling_iter >= 1");
+    *r->chains_out = nullptr;
+    const size_t t = static_cast<size_t>(r->thin);
+    samp_rows = t == 0 ? 0 : (static_cast<size_t>(a.max_sampling_iter) + t - 1) / t;
+  }
+  p.rows = samp_rows + p.warm_rows;
+  if (p.rows > 0 && a.out == nullptr) throw std::invalid_argument("out must not be null");
+  const size_t draws_offset = static_cast<size_t>(m.num_params) * p.rows;
+  if (a.out_size < a.num_chains * draws_offset) {
+    std::stringstream ss;
+    ss << "Output buffer too small. Expected at least " << a.num_chains << " chains of " << draws_offset
+       << " doubles, got " << a.out_size;
+    throw std::runtime_error(ss.str());
+  }
+  // WarmupConfigBuilder / SamplingConfigBuilder validation (config.hpp:656-850, 978-1059)
+  if (static_cast<size_t>(a.min_warmup_iter) > static_cast<size_t>(a.max_warmup_iter))
+    throw std::invalid_argument("min_iter cannot be greater than than max_iter");
+  finite_positive(a.step_size_converge_tol, "step_size_converge_tol");
+  finite_positive(a.mass_converge_tol, "mass_converge_tol");
+  finite_positive(a.mass_init_count, "mass_init_count");
+  finite_positive(a.mass_additive_smoothing, "mass_additive_smoothing");
+  finite_positive(a.max_macro_steps_target, "max_macro_steps_target");
+  probability(a.step_accept_rate_target, "step_accept_rate_target");
+  finite_positive(a.step_learning_rate, "step_learning_rate");
+  probability(a.step_gradient_decay, "step_gradient_decay");
+  probability(a.step_sq_gradient_decay, "step_sq_gradient_decay");
+  finite_positive(a.step_stabilization, "step_stabilization");
+  probability(a.step_learn_rate_decay, "step_learn_rate_decay");
+  if (static_cast<size_t>(a.min_sampling_iter) > static_cast<size_t>(a.max_sampling_iter))
+    throw std::invalid_argument("min_iter must be <= max_iter");
+  if (!(std::isfinite(a.rhat_converge_tol) && a.rhat_converge_tol > 1))
+    throw std::invalid_argument("rhat_convergence_tol must be finite and > 1");
+  finite_positive(a.max_hamiltonian_error, "max_hamiltonian_error");
+  if (a.min_micro_steps < 1) throw std::invalid_argument("min_micro_steps must be in {1, 2, ... }");
+  finite_positive(a.step_size_init, "step size");  // config.hpp:222
 
-    wn_config cfg;
-    wn_default_config(&cfg);
-    cfg.max_trajectory_doublings = max_trajectory_doublings;
-    cfg.max_step_halvings = max_step_halvings;
-    cfg.min_micro_steps = min_micro_steps;
-    cfg.max_hamiltonian_error = max_hamiltonian_error;
-    cfg.mass_init_count = mass_init_count;
-    cfg.max_macro_steps_target = max_macro_steps_target;
-    cfg.step_accept_rate_target = step_accept_rate_target;
-    cfg.step_learning_rate = step_learning_rate;
-    cfg.step_gradient_decay = step_gradient_decay;
-    cfg.step_sq_gradient_decay = step_sq_gradient_decay;
-    cfg.step_stabilization = step_stabilization;
-    cfg.step_learn_rate_decay = step_learn_rate_decay;
-    // the entry point that reproduces the reference's streams also keeps the reference's element-wise arithmetic
-    // (x86-64 -O3: every product rounded), independent of the process environment
-    if (reference_streams) cfg.fused_multiply_add = 0;
-    if (shard != nullptr) cfg.device = shard->device;
+  wn_default_config(&p.cfg);
+  p.cfg.max_trajectory_doublings = a.max_trajectory_doublings;
+  p.cfg.max_step_halvings = a.max_step_halvings;
+  p.cfg.min_micro_steps = a.min_micro_steps;
+  p.cfg.max_hamiltonian_error = a.max_hamiltonian_error;
+  p.cfg.mass_init_count = a.mass_init_count;
+  p.cfg.max_macro_steps_target = a.max_macro_steps_target;
+  p.cfg.step_accept_rate_target = a.step_accept_rate_target;
+  p.cfg.step_learning_rate = a.step_learning_rate;
+  p.cfg.step_gradient_decay = a.step_gradient_decay;
+  p.cfg.step_sq_gradient_decay = a.step_sq_gradient_decay;
+  p.cfg.step_stabilization = a.step_stabilization;
+  p.cfg.step_learn_rate_decay = a.step_learn_rate_decay;
+  // the entry point that reproduces the reference's streams also keeps the reference's element-wise arithmetic
+  // (x86-64 -O3: every product rounded), independent of the process environment
+  if (mode.reference_streams) p.cfg.fused_multiply_add = 0;
+  return p;
+}
 
-    PhaseTimer timer;
-    // (declared first of the call's resources: destroyed last, after the copies into the buffer have been waited for;
-    // started once the device allocations are done -- see below)
-    std::unique_ptr<Prefault> populate;
-    EngineGuard guard;
-    if (data != nullptr) {
-      WN_CALL(wn_engine_create_with_data(&guard.e, model, num_params, model_params, data->x, data->y, data->num_obs,
-                                         num_chains, &cfg, &call_err_));
-    } else {
-      WN_CALL(wn_engine_create(&guard.e, model, num_params, model_params, num_chains, &cfg, &call_err_));
-    }
-    wn_engine* e = guard.e;
-    const size_t D = static_cast<size_t>(num_params);
-    timer.mark("engine created");
-    // Preparation thread: what the iterations need that does not depend on the host streams -- the draw staging blocks
-    // (or the resident draw block) allocated: 0.6-1.0 s for 16-32 GiB of fresh device memory at the headline size; the
-    // caller's buffer registered if asked for -- beside the ~0.4 s the streams take on this thread.
-    const hipStream_t compute = reinterpret_cast<hipStream_t>(wn_engine_stream(e));
-    std::unique_ptr<PinnedRange> pinned;
-    std::unique_ptr<DrawSink> sink_holder;
-    std::unique_ptr<ResidentDraws> kept;
-    std::exception_ptr prep_error;
-    std::thread prep([&] {
-      try {
-        if (hipSetDevice(cfg.device) != hipSuccess) throw std::runtime_error("cannot select the device");
-        pinned = std::make_unique<PinnedRange>(out, num_chains * draws_offset * sizeof(double));
-        sink_holder = std::make_unique<DrawSink>(num_chains, rows, resident != nullptr ? warm_rows : rows, D, out, e, cfg.device);
-        if (resident != nullptr)
-          kept = std::make_unique<ResidentDraws>(num_chains, static_cast<size_t>(max_sampling_iter), D, resident->thin,
-                                                 out, rows, warm_rows, e);
-      } catch (...) {
-        prep_error = std::current_exception();
-      }
-    });
-    struct PrepJoiner {
-      std::thread& t;
-      ~PrepJoiner() {
-        if (t.joinable()) t.join();
-      }
-    } join_prep{prep};
+// ---- one shard: engine creation to the hand-over of its lengths and draws ------------------------------------------
+struct Shard {  // a contiguous block of the call's global chain ids; a one-device call is the one shard [0, C)
+  int index;    // in the Coordinator
+  size_t chain_begin, total_chains;
+  int* lengths_warmup;  // final_lengths slices of these chains
+  int* lengths_sampling;
+  const InterruptGuard* interrupt;  // the call's one SIGINT guard (null: the shard installs its own once seeded)
+};
 
-    // The reference's two host streams (wn_refstream.h): the step-size search's normals -- mt19937_64(seed_seq{seed, 2}),
-    // the engine shared by the chains in order, a fresh normal distribution per chain (walnutpy.cpp:75-80, util.hpp:288)
-    // -- are produced by a second thread while this one produces the initial positions; both hand the non-sequential
-    // half of the work to the same worker pool.
-    // -- ONLY in walnutpie_sample_device_reference_streams.  walnutpie_sample_device / _resident draw both from the
-    // counter-based generator on the device (wn_init.h: streams kStreamInitPos / kStreamInitStep keyed by `seed` and the
-    // chain id), as they draw the trajectories' variates: one sequential mt19937_64 for 67 M polar-method normals was
-    // 0.4-0.5 s of a 1.0 s call at 65 536 x 1 024 (profiles/r03/sample_device_e2e.txt) to reproduce the first two of
-    // the reference's streams bit for bit in a mode whose third stream differs anyway.
-    std::unique_ptr<wnref::Workers> pool;
-    std::vector<double> z;
-    std::thread step_stream;
-    struct Joiner {
-      std::thread& t;
-      ~Joiner() {
-        if (t.joinable()) t.join();
-      }
-    } join_step_stream{step_stream};
-    if (reference_streams) {
-      pool = std::make_unique<wnref::Workers>(wnref::usable_threads());
-      z.resize(num_chains * D);
-      step_stream = std::thread([&] {
-        std::seed_seq ss{seed, 2u};
-        std::mt19937_64 rng(ss);
-        wnref::polar_stream_fill(rng, *pool, 1.0, num_chains, D, /*fresh_per_chain=*/true, z.data());
-      });
-    }
-    // initial positions (walnutpy.cpp:176-190)
-    if (inits != nullptr) {
-      for (size_t i = 0; i < num_chains * D; ++i)
-        if (!std::isfinite(inits[i])) throw std::invalid_argument("positions must be finite");
-      WN_CALL(wn_engine_set_positions(e, inits, &call_err_));
-    } else if (reference_streams) {
-      finite_positive(init_radius, "init_scale");
-      std::vector<double> pos(num_chains * D);
-      std::seed_seq ss{seed, 1u};
-      std::mt19937_64 rng(ss);
-      // one detail::Random -- one normal distribution -- for all chains (config.hpp:261-266); x *= init_radius
-      wnref::polar_stream_fill(rng, *pool, init_radius, num_chains, D, /*fresh_per_chain=*/false, pos.data());
-      WN_CALL(wn_engine_set_positions(e, pos.data(), &call_err_));
-    } else {
-      finite_positive(init_radius, "init_scale");
-      // config.hpp:258-268, all chains at once; the stream is keyed by the GLOBAL chain id
-      WN_CALL(wn_engine_init_positions(e, seed, static_cast<uint32_t>(chain_begin), init_radius, &call_err_));
-    }
-    timer.mark(reference_streams ? "initial positions (host stream)" : "initial positions");
-    // masses (walnutpy.cpp:64-73).  NB the reference hands init_inv_metric to the builder's
-    // masses(): reproduced as is.
-    if (init_inv_metric != nullptr) {
-      WN_CALL(wn_engine_set_masses(e, init_inv_metric, &call_err_));
-    } else {
-      WN_CALL(wn_engine_init_masses_from_grad(e, mass_additive_smoothing, &call_err_));
-    }
-    {
-      std::vector<double> steps(num_chains, step_size_init);
-      WN_CALL(wn_engine_set_step_sizes(e, steps.data(), &call_err_));
-    }
-    timer.mark("initial masses");
-    // adapt_step_build (walnutpy.cpp:75-80): on the normals the second thread produced, or with the device's own
-    if (reference_streams) {
-      if (step_stream.joinable()) step_stream.join();
-      pool->wait_idle();
-      WN_CALL(wn_engine_adapt_step_with_normals(e, z.data(), &call_err_));
-      std::vector<double>().swap(z);
-    } else {
-      WN_CALL(wn_engine_adapt_step(e, seed, static_cast<uint32_t>(chain_begin), &call_err_));
-    }
-    timer.mark(reference_streams ? "step-size search (host stream)" : "step-size search");
-    // walnutpy.cpp:82: walnuts<mt19937_64>(seed + id + num_chains, ...)
-    if (reference_streams) {
-      WN_CALL(wn_engine_seed_reference_streams(e, static_cast<uint64_t>(seed) + id + num_chains, &call_err_));
-    } else {
-      WN_CALL(wn_engine_seed(e, static_cast<uint64_t>(seed) + id + total_chains, static_cast<uint32_t>(chain_begin),
-                             &call_err_));
-    }
+// initial positions given by the caller (walnutpy.cpp:176-190); false: they are to be drawn
+bool set_given_positions(wn_engine* e, const SampleArgs& a, size_t D) {
+  if (a.inits == nullptr) {
+    finite_positive(a.init_radius, "init_scale");
+    return false;
+  }
+  for (size_t i = 0; i < a.num_chains * D; ++i)
+    if (!std::isfinite(a.inits[i])) throw std::invalid_argument("positions must be finite");
+  WN_CALL(wn_engine_set_positions(e, a.inits, &call_err_));
+  return true;
+}
+// masses (walnutpy.cpp:64-73; NB the reference hands init_inv_metric to the builder's masses(): reproduced as is) and
+// the initial step sizes
+void set_masses_and_step_sizes(wn_engine* e, const SampleArgs& a) {
+  if (a.init_inv_metric != nullptr) {
+    WN_CALL(wn_engine_set_masses(e, a.init_inv_metric, &call_err_));
+  } else {
+    WN_CALL(wn_engine_init_masses_from_grad(e, a.mass_additive_smoothing, &call_err_));
+  }
+  std::vector<double> steps(a.num_chains, a.step_size_init);
+  WN_CALL(wn_engine_set_step_sizes(e, steps.data(), &call_err_));
+}
 
-    // walnutpy.cpp: interrupt::walnutpy_interrupt_handler on the stack of the call (one guard for all shards)
-    std::unique_ptr<InterruptGuard> own_guard;
-    if (shard == nullptr || shard->interrupt == nullptr) own_guard = std::make_unique<InterruptGuard>();
-    const InterruptGuard& interrupt = own_guard ? *own_guard : *shard->interrupt;
-    timer.mark("chains seeded");
-    prep.join();
-    if (prep_error) std::rethrow_exception(prep_error);
-    DrawSink& sink = *sink_holder;
-    RunAhead pace(compute);
-    timer.mark("preparation thread joined (output registered, draw blocks allocated)");
-    // The helpers start HERE, not at the call's entry: page population and hipMalloc both go through the process's
-    // address-space lock, and with the helpers running the engine's and the staging blocks' allocations took 0.9 s
-    // instead of 0.03 s (profiles/r04/prefault_ab.txt).  From here on the call only launches kernels and copies.
-    // (Only for the sink's direct copies: the pinned ring's scatter threads take their first-touch faults in parallel
-    // by themselves, and the helpers beside them only contend -- 0.80-0.83 s with both against 0.51 s with the ring
-    // alone, same file.)
-    if (!sink.uses_ring())
-      populate = std::make_unique<Prefault>(out, num_chains * draws_offset * sizeof(double),
-                                            static_cast<double>(num_chains) / static_cast<double>(std::max<size_t>(1, total_chains)));
-    // (progress lines: shard 0 speaks for all chains)
-    Printer printer{shard != nullptr && shard->shard != 0 ? nullptr : print, static_cast<size_t>(refresh)};
-    // Consecutive iterations between two looks of a controller go out as ONE launch (wn_engine_*_steps: the workgroup
-    // that fetched a chain runs them back to back -- the chains are independent, adapt.hpp:116-127 / sampler.hpp:82-93
-    // are per-chain loops): the launch and its tail, the last chains finishing while the chip drains, are paid once
-    // per launch.  Host-fed reference streams cover one transition per launch.
-    const int fuse_limit = reference_streams ? 1 : kMaxFusedTransitions;
+// The chains' initial state from the counter-based generator on the device (wn_init.h: streams kStreamInitPos /
+// kStreamInitStep keyed by `seed` and the GLOBAL chain id), as the trajectories' variates are drawn: positions
+// (config.hpp:258-268), step-size search (walnutpy.cpp:75-80) and the chains' seeds (walnutpy.cpp:82:
+// walnuts<mt19937_64>(seed + id + num_chains, ...)).
+void initial_state(wn_engine* e, const SampleArgs& a, size_t D, const Shard& shard, PhaseTimer& timer) {
+  const auto first = static_cast<uint32_t>(shard.chain_begin);
+  if (!set_given_positions(e, a, D)) WN_CALL(wn_engine_init_positions(e, a.seed, first, a.init_radius, &call_err_));
+  timer.mark("initial positions");
+  set_masses_and_step_sizes(e, a);
+  timer.mark("initial masses");
+  WN_CALL(wn_engine_adapt_step(e, a.seed, first, &call_err_));
+  timer.mark("step-size search");
+  WN_CALL(wn_engine_seed(e, static_cast<uint64_t>(a.seed) + a.id + shard.total_chains, first, &call_err_));
+}
+
+// walnutpie_sample_device_reference_streams: the same from the reference's two host streams (wn_refstream.h) and its
+// chain seeding.  The step-size search's normals -- mt19937_64(seed_seq{seed, 2}), the engine shared by the chains in
+// order, a fresh normal distribution per chain (walnutpy.cpp:75-80, util.hpp:288) -- are produced by a second thread
+// while this one produces the initial positions; both hand the non-sequential half of the work to the same worker pool.
+// (Only in this mode: one sequential mt19937_64 for 67 M polar-method normals was 0.4-0.5 s of a 1.0 s call at
+// 65 536 x 1 024 (profiles/r03/sample_device_e2e.txt) to reproduce the first two of the reference's streams bit for bit
+// in a mode whose third stream differs anyway.)
+void initial_state_reference_streams(wn_engine* e, const SampleArgs& a, size_t D, PhaseTimer& timer) {
+  const size_t C = a.num_chains;
+  wnref::Workers pool(wnref::usable_threads());
+  std::vector<double> z(C * D);
+  std::future<void> step_stream = std::async(std::launch::async, [&] {  // (its destructor waits for it)
+    std::seed_seq ss{a.seed, 2u};
+    std::mt19937_64 rng(ss);
+    wnref::polar_stream_fill(rng, pool, 1.0, C, D, /*fresh_per_chain=*/true, z.data());
+  });
+  if (!set_given_positions(e, a, D)) {
+    std::vector<double> pos(C * D);
+    std::seed_seq ss{a.seed, 1u};
+    std::mt19937_64 rng(ss);
+    // one detail::Random -- one normal distribution -- for all chains (config.hpp:261-266); x *= init_radius
+    wnref::polar_stream_fill(rng, pool, a.init_radius, C, D, /*fresh_per_chain=*/false, pos.data());
+    WN_CALL(wn_engine_set_positions(e, pos.data(), &call_err_));
+  }
+  timer.mark("initial positions (host stream)");
+  set_masses_and_step_sizes(e, a);
+  timer.mark("initial masses");
+  step_stream.get();
+  pool.wait_idle();
+  WN_CALL(wn_engine_adapt_step_with_normals(e, z.data(), &call_err_));
+  timer.mark("step-size search (host stream)");
+  WN_CALL(wn_engine_seed_reference_streams(e, static_cast<uint64_t>(a.seed) + a.id + C, &call_err_));
+}
+
+// The iteration loops of one shard.  Consecutive iterations between two looks of a controller go out as ONE launch
+// (wn_engine_*_steps: the workgroup that fetched a chain runs them back to back -- the chains are independent,
+// adapt.hpp:116-127 / sampler.hpp:82-93 are per-chain loops): the launch and its tail, the last chains finishing while
+// the chip drains, are paid once per launch.  Host-fed reference streams cover one transition per launch.
+struct Iterations {
+  wn_engine* e;
+  const SampleArgs& a;
+  size_t D;
+  const Shard& shard;
+  Coordinator& coord;
+  const InterruptGuard& interrupt;
+  DrawSink& sink;
+  ResidentDraws* kept;  // resident calls: the sampling draws' block
+  RunAhead& pace;
+  Printer& printer;
+  int fuse_limit;
+
+  // AdaptWorker loop (adapt.hpp:116-127) with controller_loop (adapt.hpp:172-229) on the snapshots published every
+  // publish_stride = 5 iterations
+  void warmup() {
     constexpr int publish_stride = 5;  // adapt.hpp: snapshots every 5 iterations
-    for (int it = 0; it < max_warmup_iter;) {  // AdaptWorker loop, adapt.hpp:116-127
+    for (int it = 0; it < a.max_warmup_iter;) {
       interrupt.throw_if_interrupted();
       pace.before_enqueue();
-      int n = std::min({fuse_limit, max_warmup_iter - it, publish_stride - it % publish_stride});
-      if (save_warmup) n = static_cast<int>(std::min<size_t>(static_cast<size_t>(n), sink.room()));
-      double* dst = save_warmup ? sink.next_row() : nullptr;
+      int n = std::min({fuse_limit, a.max_warmup_iter - it, publish_stride - it % publish_stride});
+      if (a.save_warmup) n = static_cast<int>(std::min<size_t>(static_cast<size_t>(n), sink.room()));
+      double* dst = a.save_warmup ? sink.next_row() : nullptr;
       WN_CALL(wn_engine_warmup_steps(e, n, dst, static_cast<int64_t>(sink.stride()), static_cast<int64_t>(D), &call_err_));
-      if (save_warmup) sink.rows_done(static_cast<size_t>(n));
+      if (a.save_warmup) sink.rows_done(static_cast<size_t>(n));
       pace.after_enqueue();
-      for (int k = 0; k < n; ++k) {  // (a Ctrl-C raised from inside a progress callback ends the call at once)
-        printer.progress(total_chains);
-        interrupt.throw_if_interrupted();
-      }
+      progress(n);
       it += n;
-      // controller_loop (adapt.hpp:172-229) on the snapshots published every publish_stride = 5 iterations
-      if (it >= min_warmup_iter && it < max_warmup_iter && it % publish_stride == 0) {
-        if (shard != nullptr) {
-          if (shard->coord->warmup_converged(shard->shard, e, total_chains, step_size_converge_tol, mass_converge_tol)) break;
-        } else {
-          double rel_step = 0, rel_mass = 0;
-          WN_CALL(wn_engine_warmup_spread(e, &rel_step, &rel_mass, &call_err_));
-          if (rel_mass <= mass_converge_tol && rel_step <= step_size_converge_tol) break;
-        }
-      }
+      if (it >= a.min_warmup_iter && it < a.max_warmup_iter && it % publish_stride == 0 &&
+          coord.warmup_converged(shard.index, e, shard.total_chains, a.step_size_converge_tol, a.mass_converge_tol))
+        break;
     }
-    const size_t written_warmup = sink.written();
-    if (kept) kept->set_first_row(written_warmup);
-    if (timer.on) WN_CALL(wn_engine_synchronize(e, &call_err_));
-    timer.mark("warmup iterations");
-    WN_CALL(wn_engine_freeze(e, &call_err_));  // on_warmup_complete, handlers.hpp:91-101
-    printer.in_warmup = false;
-    if (stepsize_out != nullptr) WN_CALL(wn_engine_get_step_sizes(e, stepsize_out, &call_err_));
-    if (inv_metric_out != nullptr) WN_CALL(wn_engine_get_inv_mass(e, inv_metric_out, &call_err_));
+  }
+
+  // ChainWorker loop (sampler.hpp:82-93) with controller_loop (sampler.hpp:117-158): R-hat of the log density once
+  // every chain has min_iter draws.  The reference's controller looks on a 1 ms timer, not after every draw: here every
+  // `rhat_stride` iterations (each look is a handful of small launches and a blocking read-back that would otherwise
+  // serialise every transition with the host).  Returns the iterations run.
+  size_t sampling() {
     size_t sampled = 0;
-    // controller_loop (sampler.hpp:117-158): R-hat of the log density once every chain has min_iter draws.  The
-    // reference's controller looks on a 1 ms timer, not after every draw: here every `rhat_stride` iterations
-    // (each look is a handful of small launches and a blocking read-back that would otherwise serialise every
-    // transition with the host).
-    constexpr int rhat_stride = 5;
-    const auto controller_looks_after = [&](int it) {
-      return it >= min_sampling_iter && it >= 2 && it < max_sampling_iter && total_chains > 1 &&
-             (it - min_sampling_iter) % rhat_stride == 0;
-    };
-    for (int it = 0; it < max_sampling_iter;) {  // ChainWorker loop, sampler.hpp:82-93
+    for (int it = 0; it < a.max_sampling_iter;) {
       interrupt.throw_if_interrupted();
       pace.before_enqueue();
       int n = 1;  // up to the controller's next look
-      while (n < fuse_limit && it + n < max_sampling_iter && !controller_looks_after(it + n)) ++n;
+      while (n < fuse_limit && it + n < a.max_sampling_iter && !controller_looks_after(it + n)) ++n;
       if (kept) {
         WN_CALL(wn_engine_sample_steps(e, n, kept->next_row(), kept->stride(), static_cast<int64_t>(D), &call_err_));
         for (int k = 0; k < n; ++k) kept->row_done();
@@ -1076,93 +1043,304 @@ static int sample_device_impl(
       }
       sampled += static_cast<size_t>(n);
       pace.after_enqueue();
-      for (int k = 0; k < n; ++k) {  // (a Ctrl-C raised from inside a progress callback ends the call at once)
-        printer.progress(total_chains);
-        interrupt.throw_if_interrupted();
-      }
+      progress(n);
       it += n;
       if (controller_looks_after(it)) {
-        double rhat = 0;
-        if (shard != nullptr) {
-          rhat = shard->coord->rhat(shard->shard, e);
-        } else {
-          WN_CALL(wn_engine_rhat(e, &rhat, &call_err_));
-        }
-        if (printer.print != nullptr && refresh != 0) {
+        const double rhat = coord.rhat(shard.index, e);
+        if (printer.print != nullptr && a.refresh != 0) {
           std::stringstream ss;
           ss << "Controller: R-hat at " << std::setprecision(10) << rhat << std::endl;  // handlers.hpp:160-176
           const std::string msg = ss.str();
-          print(msg.c_str(), msg.length(), false);
+          printer.print(msg.c_str(), msg.length(), false);
         }
-        if (rhat <= rhat_converge_tol) break;
+        if (rhat <= a.rhat_converge_tol) break;
       }
     }
-    WN_CALL(wn_engine_check(e, &call_err_));
-    timer.mark("sampling iterations");
-    sink.finish();
-    if (kept) kept->finish();
-    timer.mark("draws in the caller's buffer");
-    interrupt.throw_if_interrupted();
-    {  // walnutpy.cpp:215-218
-      int* lw = shard != nullptr ? shard->lengths_warmup : final_lengths;
-      int* ls = shard != nullptr ? shard->lengths_sampling : final_lengths + num_chains;
-      for (size_t c = 0; c < num_chains; ++c) {
-        lw[c] = static_cast<int>(written_warmup);
-        ls[c] = static_cast<int>(sampled);
-      }
-    }
-    if (kept) {
-      // the block changes hands: a wn_chains of `sampled` draws per chain that frees it when it is destroyed
-      WN_CALL(wn_engine_synchronize(e, &call_err_));
-      std::vector<int64_t> lengths(num_chains, static_cast<int64_t>(sampled));
-      double* block = kept->release();
-      WalnutpyError* adopt_err = nullptr;
-      if (wn_chains_adopt(resident->chains_out, block, num_chains, static_cast<size_t>(max_sampling_iter), D,
-                          static_cast<int64_t>(max_sampling_iter) * static_cast<int64_t>(D), lengths.data(), cfg.device,
-                          &adopt_err) != 0) {
-        (void)hipFree(block);
-        rethrow(adopt_err);
-      }
-    }
-    timer.mark("lengths written, draw block handed over");
-    sink_holder.reset();
-    kept.reset();
-    wn_engine_destroy(guard.e);
-    guard.e = nullptr;
-    timer.mark("engine and staging memory released");
-    return 0;
-  } catch (const ShardAborted&) {
-    if (err) *err = nullptr;  // (another shard holds the error this call reports)
-  } catch (const InterruptException&) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error("", interrupt));
-  } catch (const std::invalid_argument& ex) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(ex.what(), config));
-  } catch (const std::exception& ex) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(ex.what(), generic));
-  } catch (...) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error("Unknown error", generic));
+    return sampled;
   }
-  return -1;
+
+ private:
+  void progress(int n) {
+    for (int k = 0; k < n; ++k) {  // (a Ctrl-C raised from inside a progress callback ends the call at once)
+      printer.progress(shard.total_chains);
+      interrupt.throw_if_interrupted();
+    }
+  }
+  bool controller_looks_after(int it) const {
+    return it >= a.min_sampling_iter && it >= 2 && it < a.max_sampling_iter && shard.total_chains > 1 &&
+           (it - a.min_sampling_iter) % rhat_stride == 0;
+  }
+  static constexpr int rhat_stride = 5;
+};
+
+// `a` is already this shard's slice of the call (its chains, its rows of the caller's buffers) and `plan` its
+// validated configuration, cfg.device its device.  Progress lines come from whichever shard was given `print`.
+void run_shard(const Model& m, const SampleArgs& a, const Mode& mode, const Plan& plan, const Shard& shard,
+               Coordinator& coord) {
+  const size_t C = a.num_chains, D = static_cast<size_t>(m.num_params);
+  const size_t out_bytes = C * D * plan.rows * sizeof(double);
+  const int device = plan.cfg.device;
+  PhaseTimer timer;
+  // (declared first of the call's resources: destroyed last, after the copies into the buffer have been waited for;
+  // started once the device allocations are done -- see below)
+  std::unique_ptr<Prefault> populate;
+  EngineGuard guard;
+  if (mode.data != nullptr) {
+    WN_CALL(wn_engine_create_with_data(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
+                                       mode.data->num_obs, C, &plan.cfg, &call_err_));
+  } else {
+    WN_CALL(wn_engine_create(&guard.e, m.id, m.num_params, m.params, C, &plan.cfg, &call_err_));
+  }
+  wn_engine* e = guard.e;
+  timer.mark("engine created");
+  // Preparation thread: what the iterations need that does not depend on the host streams -- the draw staging blocks
+  // (or the resident draw block) allocated: 0.6-1.0 s for 16-32 GiB of fresh device memory at the headline size; the
+  // caller's buffer registered if asked for -- beside the ~0.4 s the streams take on this thread.
+  const hipStream_t compute = reinterpret_cast<hipStream_t>(wn_engine_stream(e));
+  std::unique_ptr<PinnedRange> pinned;
+  std::unique_ptr<DrawSink> sink_holder;
+  std::unique_ptr<ResidentDraws> kept;
+  std::future<void> prep = std::async(std::launch::async, [&] {  // (its destructor waits for it)
+    if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("cannot select the device");
+    pinned = std::make_unique<PinnedRange>(a.out, out_bytes);
+    sink_holder = std::make_unique<DrawSink>(C, plan.rows, mode.resident != nullptr ? plan.warm_rows : plan.rows, D,
+                                             a.out, e, device);
+    if (mode.resident != nullptr)
+      kept = std::make_unique<ResidentDraws>(C, static_cast<size_t>(a.max_sampling_iter), D, mode.resident->thin, a.out,
+                                             plan.rows, plan.warm_rows, e);
+  });
+
+  if (mode.reference_streams) initial_state_reference_streams(e, a, D, timer);
+  else initial_state(e, a, D, shard, timer);
+  // walnutpy.cpp: interrupt::walnutpy_interrupt_handler on the stack of the call
+  std::optional<InterruptGuard> own_interrupt;
+  if (shard.interrupt == nullptr) own_interrupt.emplace();
+  const InterruptGuard& interrupt = shard.interrupt != nullptr ? *shard.interrupt : *own_interrupt;
+  timer.mark("chains seeded");
+  prep.get();
+  DrawSink& sink = *sink_holder;
+  RunAhead pace(compute);
+  timer.mark("preparation thread joined (output registered, draw blocks allocated)");
+  // The helpers start HERE, not at the call's entry: page population and hipMalloc both go through the process's
+  // address-space lock, and with the helpers running the engine's and the staging blocks' allocations took 0.9 s
+  // instead of 0.03 s (profiles/r04/prefault_ab.txt).  From here on the call only launches kernels and copies.
+  // (Only for the sink's direct copies: the pinned ring's scatter threads take their first-touch faults in parallel
+  // by themselves, and the helpers beside them only contend -- 0.80-0.83 s with both against 0.51 s with the ring
+  // alone, same file.)
+  if (!sink.uses_ring())
+    populate = std::make_unique<Prefault>(
+        a.out, out_bytes, static_cast<double>(C) / static_cast<double>(std::max<size_t>(1, shard.total_chains)));
+  Printer printer{a.print, static_cast<size_t>(a.refresh)};
+  Iterations iterations{e,    a,          D,      shard,   coord, interrupt, sink, kept.get(), pace, printer,
+                        mode.reference_streams ? 1 : kMaxFusedTransitions};
+  iterations.warmup();
+  const size_t written_warmup = sink.written();
+  if (kept) kept->set_first_row(written_warmup);
+  if (timer.on) WN_CALL(wn_engine_synchronize(e, &call_err_));
+  timer.mark("warmup iterations");
+  WN_CALL(wn_engine_freeze(e, &call_err_));  // on_warmup_complete, handlers.hpp:91-101
+  printer.in_warmup = false;
+  if (a.stepsize_out != nullptr) WN_CALL(wn_engine_get_step_sizes(e, a.stepsize_out, &call_err_));
+  if (a.inv_metric_out != nullptr) WN_CALL(wn_engine_get_inv_mass(e, a.inv_metric_out, &call_err_));
+  const size_t sampled = iterations.sampling();
+  WN_CALL(wn_engine_check(e, &call_err_));
+  timer.mark("sampling iterations");
+  sink.finish();
+  if (kept) kept->finish();
+  timer.mark("draws in the caller's buffer");
+  interrupt.throw_if_interrupted();
+  for (size_t c = 0; c < C; ++c) {  // walnutpy.cpp:215-218
+    shard.lengths_warmup[c] = static_cast<int>(written_warmup);
+    shard.lengths_sampling[c] = static_cast<int>(sampled);
+  }
+  if (kept) {
+    // the block changes hands: a wn_chains of `sampled` draws per chain that frees it when it is destroyed
+    WN_CALL(wn_engine_synchronize(e, &call_err_));
+    std::vector<int64_t> lengths(C, static_cast<int64_t>(sampled));
+    const size_t S = static_cast<size_t>(a.max_sampling_iter);
+    double* block = kept->release();
+    WalnutpyError* adopt_err = nullptr;
+    if (wn_chains_adopt(mode.resident->chains_out, block, C, S, D, static_cast<int64_t>(S * D), lengths.data(), device,
+                        &adopt_err) != 0) {
+      (void)hipFree(block);
+      rethrow(adopt_err);
+    }
+  }
+  timer.mark("lengths written, draw block handed over");
+  sink_holder.reset();
+  kept.reset();
+  wn_engine_destroy(guard.e);
+  guard.e = nullptr;
+  timer.mark("engine and staging memory released");
 }
 
-#define WN_SAMPLE_ARGS                                                                                            \
-  model, model_params, num_params, inits, num_chains, seed, id, init_radius, init_inv_metric, min_warmup_iter,   \
-      max_warmup_iter, min_sampling_iter, max_sampling_iter, max_trajectory_doublings, max_step_halvings,        \
-      min_micro_steps, max_hamiltonian_error, step_size_converge_tol, mass_converge_tol, rhat_converge_tol,      \
-      mass_init_count, mass_additive_smoothing, max_macro_steps_target, step_size_init, step_accept_rate_target, \
-      step_learning_rate, step_gradient_decay, step_sq_gradient_decay, step_stabilization, step_learn_rate_decay, \
-      save_warmup, out, out_size, final_lengths, stepsize_out, inv_metric_out, refresh, print, err
-#define WN_SAMPLE_PARAMS                                                                                          \
-  int model, const double *model_params, int num_params, const double *inits, size_t num_chains,                 \
-      unsigned int seed, unsigned int id, double init_radius, const double *init_inv_metric, int min_warmup_iter, \
-      int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,           \
-      int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,   \
-      double mass_converge_tol, double rhat_converge_tol, double mass_init_count,                                \
-      double mass_additive_smoothing, double max_macro_steps_target, double step_size_init,                      \
-      double step_accept_rate_target, double step_learning_rate, double step_gradient_decay,                     \
-      double step_sq_gradient_decay, double step_stabilization, double step_learn_rate_decay, bool save_warmup,  \
-      double *out, size_t out_size, int *final_lengths, double *stepsize_out, double *inv_metric_out,            \
-      int refresh, PRINT_CALLBACK print, WalnutpyError **err
+int sample_one(const Model& m, const SampleArgs& a, const Mode& mode, WalnutpyError** err) {
+  try {
+    const Plan plan = validate(m, a, mode);
+    Coordinator one(1, static_cast<size_t>(m.num_params));
+    run_shard(m, a, mode, plan, Shard{0, 0, a.num_chains, a.final_lengths, a.final_lengths + a.num_chains, nullptr}, one);
+    return 0;
+  } catch (...) {
+    return report_exception(err);
+  }
+}
+
+// ---- several devices behind one call --------------------------------------------------------------------------------
+// The resident shards' blocks gathered: shard s's [count_s][S][D] block is rows [begin_s, begin_s + count_s) of the
+// whole [C][S][D] block.  One destination: devices[0] (gather), or every listed device (all_gather: the north star's
+// exchange -- every device ends with every shard's draws).  Every (destination, source) pair is its own hipMemcpyPeerAsync on its
+// own stream of the destination, so the inbound copies of a device run side by side, each over the xGMI link of its
+// source -- not one after the other on one in-order stream.  Peer access is switched on per pair first: without it the
+// runtime stages a peer copy through host memory.  (Unmeasured on more than one physical device: this pool has one GPU
+// per box; the one-device tests list a device several times, where a "peer" copy is a local copy.)
+void gather(const std::vector<wn_chains*>& shard_chains, const int* devices, const ResidentRequest& resident, size_t C,
+            size_t S, size_t D, const int* lengths_sampling) {
+  const int num_devices = static_cast<int>(shard_chains.size());
+  struct RestoreDevice {  // the gather selects the destinations: the calling thread gets its current device back
+    int before = -1;
+    RestoreDevice() { if (hipGetDevice(&before) != hipSuccess) before = -1; }
+    ~RestoreDevice() { if (before >= 0) (void)hipSetDevice(before); }
+  } restore_device;
+  const int destinations = resident.all_gather ? num_devices : 1;
+  std::vector<size_t> first(static_cast<size_t>(num_devices) + 1, 0);
+  for (int s = 0; s < num_devices; ++s)
+    first[static_cast<size_t>(s) + 1] = first[static_cast<size_t>(s)] + wn_chains_num_chains(shard_chains[static_cast<size_t>(s)]);
+  std::vector<DevBlock> whole(static_cast<size_t>(destinations));
+  std::vector<std::unique_ptr<Stream>> copies;
+  for (int d = 0; d < destinations; ++d) {
+    const int dst = devices[d];
+    if (hipSetDevice(dst) != hipSuccess) throw std::runtime_error("cannot select the device");
+    if (!whole[static_cast<size_t>(d)].alloc(C * S * D)) throw std::runtime_error("cannot allocate the gathered draw block");
+    for (int s = 0; s < num_devices; ++s) {
+      const int src = devices[s];
+      if (src != dst) {
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, dst, src) != hipSuccess || can == 0) {
+          std::stringstream ss;
+          ss << "device " << dst << " has no peer-to-peer path to device " << src
+             << ": the shards' draws cannot be gathered on it (list devices of one xGMI hive)";
+          throw std::runtime_error(ss.str());
+        }
+        const hipError_t en = hipDeviceEnablePeerAccess(src, 0);
+        if (en != hipSuccess && en != hipErrorPeerAccessAlreadyEnabled) throw std::runtime_error("cannot enable peer access");
+        (void)hipGetLastError();  // (an "already enabled" is not an error to carry along)
+      }
+      copies.push_back(std::make_unique<Stream>());
+      copies.back()->create();
+      const size_t count = first[static_cast<size_t>(s) + 1] - first[static_cast<size_t>(s)];
+      if (hipMemcpyPeerAsync(whole[static_cast<size_t>(d)].p + first[static_cast<size_t>(s)] * S * D, dst,
+                             wn_chains_device_draws(shard_chains[static_cast<size_t>(s)]), src,
+                             count * S * D * sizeof(double), copies.back()->s) != hipSuccess)
+        throw std::runtime_error("gathering the shards' draws failed");
+    }
+  }
+  for (auto& c : copies)
+    if (hipStreamSynchronize(c->s) != hipSuccess) throw std::runtime_error("gathering the shards' draws failed");
+  std::vector<int64_t> lengths(lengths_sampling, lengths_sampling + C);
+  for (int d = 0; d < destinations; ++d) resident.chains_out[d] = nullptr;
+  for (int d = 0; d < destinations; ++d) {
+    double* block = whole[static_cast<size_t>(d)].release();
+    WalnutpyError* adopt_err = nullptr;
+    if (wn_chains_adopt(&resident.chains_out[d], block, C, S, D, static_cast<int64_t>(S * D), lengths.data(), devices[d],
+                        &adopt_err) != 0) {
+      (void)hipFree(block);
+      for (int k = 0; k < d; ++k) {  // (nothing half-built is handed back)
+        wn_chains_destroy(resident.chains_out[k]);
+        resident.chains_out[k] = nullptr;
+      }
+      rethrow(adopt_err);
+    }
+  }
+}
+
+// walnutpie_sample_device over several devices of the node: one host thread, engine and stream per entry of `devices`
+// (an ordinal may repeat: two shards on one device overlap each other's launch tails), contiguous shards of the global
+// chain ids, every shard writing its own slice of the caller's buffers.  Results do not depend on the sharding: the
+// random streams are keyed by global chain id, the controllers look at all chains (Coordinator).  `resident`: every
+// shard keeps its sampling draws in a block on ITS device, gathered when all shards are done (above) and handed over as
+// one wn_chains for the wn_summary_* functions.
+int sample_multi(const Model& m, const SampleArgs& a, const ResidentRequest* resident, const int* devices,
+                 int num_devices, WalnutpyError** err) {
+  std::vector<wn_chains*> shard_chains(static_cast<size_t>(std::max(num_devices, 0)), nullptr);
+  struct ChainsGuard {
+    std::vector<wn_chains*>& v;
+    ~ChainsGuard() {
+      for (auto* c : v)
+        if (c != nullptr) wn_chains_destroy(c);
+    }
+  } chains_guard{shard_chains};
+  try {
+    if (devices == nullptr || num_devices < 1) throw std::invalid_argument("devices must name at least one device");
+    if (resident != nullptr) {
+      if (resident->chains_out == nullptr) throw std::invalid_argument("chains_out must not be null");
+      for (int d = 0; d < (resident->all_gather ? num_devices : 1); ++d) resident->chains_out[d] = nullptr;
+    }
+    if (a.num_chains < static_cast<size_t>(num_devices)) throw std::invalid_argument("fewer chains than devices");
+    int visible = 0;
+    if (hipGetDeviceCount(&visible) != hipSuccess) throw std::runtime_error("cannot count the devices");
+    for (int s = 0; s < num_devices; ++s)
+      if (devices[s] < 0 || devices[s] >= visible) throw std::invalid_argument("device ordinal out of range");
+    const Plan plan = validate(m, a, Mode{false, resident, nullptr});
+    const size_t C = a.num_chains, D = static_cast<size_t>(m.num_params);
+    InterruptGuard guard;
+    Coordinator coord(num_devices, D);
+    std::vector<WalnutpyError*> errors(static_cast<size_t>(num_devices), nullptr);
+    std::vector<int> rcs(static_cast<size_t>(num_devices), 0);
+    std::vector<std::thread> threads;
+    const size_t base = C / static_cast<size_t>(num_devices), extra = C % static_cast<size_t>(num_devices);
+    size_t begin = 0;
+    for (int s = 0; s < num_devices; ++s) {
+      const size_t count = base + (static_cast<size_t>(s) < extra ? 1 : 0);
+      const auto slice = [&](auto* p, size_t per_chain) { return p == nullptr ? nullptr : p + begin * per_chain; };
+      SampleArgs sa = a;
+      sa.num_chains = count;
+      sa.inits = slice(a.inits, D);
+      sa.init_inv_metric = slice(a.init_inv_metric, D);
+      sa.out = slice(a.out, plan.rows * D);
+      sa.out_size = count * plan.rows * D;
+      sa.stepsize_out = slice(a.stepsize_out, 1);
+      sa.inv_metric_out = slice(a.inv_metric_out, D);
+      sa.final_lengths = nullptr;  // (the shard's two slices of it are in `shard`)
+      sa.print = s == 0 ? a.print : nullptr;  // (progress lines: shard 0 speaks for all chains)
+      Plan p = plan;
+      p.cfg.device = devices[s];
+      const Shard shard{s, begin, C, a.final_lengths + begin, a.final_lengths + C + begin, &guard};
+      threads.emplace_back([&, sa, p, shard, s] {
+        const ResidentRequest shard_req{resident != nullptr ? resident->thin : 0, &shard_chains[static_cast<size_t>(s)]};
+        try {
+          run_shard(m, sa, Mode{false, resident != nullptr ? &shard_req : nullptr, nullptr}, p, shard, coord);
+        } catch (...) {
+          rcs[s] = report_exception(&errors[s]);
+          coord.abandon();
+        }
+      });
+      begin += count;
+    }
+    for (auto& t : threads) t.join();
+    // the first shard that failed with an error of its own speaks for the call
+    int rc = 0;
+    for (int s = 0; s < num_devices; ++s) {
+      if (rcs[s] != 0 && errors[s] != nullptr && rc == 0) {
+        rc = -1;
+        if (err) *err = errors[s];
+        else walnutpie_destroy_error(errors[s]);
+        errors[s] = nullptr;
+      }
+    }
+    for (auto* e : errors)
+      if (e != nullptr) walnutpie_destroy_error(e);
+    if (rc == 0)
+      for (int s = 0; s < num_devices; ++s)
+        if (rcs[s] != 0) throw std::runtime_error("a shard ended without reporting its error");
+    if (rc == 0 && resident != nullptr)
+      gather(shard_chains, devices, *resident, C, static_cast<size_t>(a.max_sampling_iter), D, a.final_lengths + C);
+    return rc;
+  } catch (...) {
+    return report_exception(err);
+  }
+}
+
+}  // namespace
 
 // (internal, for the tests) the host streams above as a function: `count_per_chain` normals for each of `num_chains`
 // chains from mt19937_64(seed_seq{seed, stream}), one distribution for all chains or a fresh one per chain
@@ -1189,271 +1367,58 @@ int refuse_host_model(const char* symbol, WalnutpyError** err) {
 }
 }  // namespace
 extern "C" int walnutpie_sample_cfunc(WN_LOGP_CFUNC, void*, int, const double*, WN_REFERENCE_SAMPLING_PARAMS) {
-  (void)num_chains, (void)seed, (void)id, (void)init_radius, (void)init_inv_metric, (void)min_warmup_iter;
-  (void)max_warmup_iter, (void)min_sampling_iter, (void)max_sampling_iter, (void)max_trajectory_doublings;
-  (void)max_step_halvings, (void)min_micro_steps, (void)max_hamiltonian_error, (void)step_size_converge_tol;
-  (void)mass_converge_tol, (void)rhat_converge_tol, (void)mass_init_count, (void)mass_additive_smoothing;
-  (void)max_macro_steps_target, (void)step_size_init, (void)step_accept_rate_target, (void)step_learning_rate;
-  (void)step_gradient_decay, (void)step_sq_gradient_decay, (void)step_stabilization, (void)step_learn_rate_decay;
-  (void)save_warmup, (void)out, (void)out_size, (void)final_lengths, (void)stepsize_out, (void)inv_metric_out;
-  (void)refresh, (void)print;
   return refuse_host_model("walnutpie_sample_cfunc", err);
 }
 extern "C" int walnutpie_sample_bridgestan(const char*, const char*, STREAM_CALLBACK, unsigned int, const char*,
                                            WN_REFERENCE_SAMPLING_PARAMS) {
-  (void)num_chains, (void)seed, (void)id, (void)init_radius, (void)init_inv_metric, (void)min_warmup_iter;
-  (void)max_warmup_iter, (void)min_sampling_iter, (void)max_sampling_iter, (void)max_trajectory_doublings;
-  (void)max_step_halvings, (void)min_micro_steps, (void)max_hamiltonian_error, (void)step_size_converge_tol;
-  (void)mass_converge_tol, (void)rhat_converge_tol, (void)mass_init_count, (void)mass_additive_smoothing;
-  (void)max_macro_steps_target, (void)step_size_init, (void)step_accept_rate_target, (void)step_learning_rate;
-  (void)step_gradient_decay, (void)step_sq_gradient_decay, (void)step_stabilization, (void)step_learn_rate_decay;
-  (void)save_warmup, (void)out, (void)out_size, (void)final_lengths, (void)stepsize_out, (void)inv_metric_out;
-  (void)refresh, (void)print;
   return refuse_host_model("walnutpie_sample_bridgestan", err);
 }
 extern "C" char walnutpie_separator_char(void) { return '\x1C'; }  // walnutpy.cpp:224-225 (ASCII file separator)
 
-extern "C" int walnutpie_sample_device(WN_SAMPLE_PARAMS) {
-  return sample_device_impl(false, nullptr, nullptr, nullptr, WN_SAMPLE_ARGS);
+extern "C" int walnutpie_sample_device(int model, const double* model_params, int num_params, WN_SAMPLE_ARG_LIST(WN_PARAM)
+                                           WalnutpyError** err) {
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{}, err);
 }
-extern "C" int walnutpie_sample_device_reference_streams(WN_SAMPLE_PARAMS) {
-  return sample_device_impl(true, nullptr, nullptr, nullptr, WN_SAMPLE_ARGS);
+extern "C" int walnutpie_sample_device_reference_streams(int model, const double* model_params, int num_params,
+                                                         WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{true}, err);
 }
-#undef WN_SAMPLE_PARAMS
-#define WN_SAMPLE_PARAMS_NOERR                                                                                    \
-  int model, const double *model_params, int num_params, const double *inits, size_t num_chains,                 \
-      unsigned int seed, unsigned int id, double init_radius, const double *init_inv_metric, int min_warmup_iter, \
-      int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,           \
-      int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,   \
-      double mass_converge_tol, double rhat_converge_tol, double mass_init_count,                                \
-      double mass_additive_smoothing, double max_macro_steps_target, double step_size_init,                      \
-      double step_accept_rate_target, double step_learning_rate, double step_gradient_decay,                     \
-      double step_sq_gradient_decay, double step_stabilization, double step_learn_rate_decay, bool save_warmup,  \
-      double *out, size_t out_size, int *final_lengths, double *stepsize_out, double *inv_metric_out,            \
-      int refresh, PRINT_CALLBACK print
-extern "C" int walnutpie_sample_device_resident(WN_SAMPLE_PARAMS_NOERR, int thin, wn_chains** chains_out,
+extern "C" int walnutpie_sample_device_resident(int model, const double* model_params, int num_params,
+                                                WN_SAMPLE_ARG_LIST(WN_PARAM) int thin, wn_chains** chains_out,
                                                 WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out};
-  return sample_device_impl(false, &req, nullptr, nullptr, WN_SAMPLE_ARGS);
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req}, err);
 }
 // the same two calls for a model conditioned on data (x, y, num_obs after num_params)
-#define WN_DATA_SAMPLE_PARAMS_NOERR                                                                               \
-  int model, const double *model_params, int num_params, const double *x, const double *y, int num_obs,          \
-      const double *inits, size_t num_chains, unsigned int seed, unsigned int id, double init_radius,             \
-      const double *init_inv_metric, int min_warmup_iter, int max_warmup_iter, int min_sampling_iter,            \
-      int max_sampling_iter, int max_trajectory_doublings, int max_step_halvings, int min_micro_steps,           \
-      double max_hamiltonian_error, double step_size_converge_tol, double mass_converge_tol,                      \
-      double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,                          \
-      double max_macro_steps_target, double step_size_init, double step_accept_rate_target,                      \
-      double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,                      \
-      double step_stabilization, double step_learn_rate_decay, bool save_warmup, double *out, size_t out_size,  \
-      int *final_lengths, double *stepsize_out, double *inv_metric_out, int refresh, PRINT_CALLBACK print
-extern "C" int walnutpie_sample_device_data(WN_DATA_SAMPLE_PARAMS_NOERR, WalnutpyError** err) {
+extern "C" int walnutpie_sample_device_data(int model, const double* model_params, int num_params, const double* x,
+                                            const double* y, int num_obs, WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
   const SampleData data{x, y, num_obs};
-  return sample_device_impl(false, nullptr, nullptr, &data, WN_SAMPLE_ARGS);
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
 }
-extern "C" int walnutpie_sample_device_data_resident(WN_DATA_SAMPLE_PARAMS_NOERR, int thin, wn_chains** chains_out,
+extern "C" int walnutpie_sample_device_data_resident(int model, const double* model_params, int num_params,
+                                                     const double* x, const double* y, int num_obs,
+                                                     WN_SAMPLE_ARG_LIST(WN_PARAM) int thin, wn_chains** chains_out,
                                                      WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out};
   const SampleData data{x, y, num_obs};
-  return sample_device_impl(false, &req, nullptr, &data, WN_SAMPLE_ARGS);
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
 }
-#undef WN_DATA_SAMPLE_PARAMS_NOERR
-
-// walnutpie_sample_device over several devices of the node: one host thread, engine and stream per entry of `devices`
-// (an ordinal may repeat: two shards on one device overlap each other's launch tails), contiguous shards of the global
-// chain ids, every shard writing its own slice of the caller's buffers.  Results do not depend on the sharding: the
-// random streams are keyed by global chain id, the controllers look at all chains (Coordinator).
-// `resident` (walnutpie_sample_device_multi_resident): every shard keeps its sampling draws in a block on ITS device;
-// when all shards are done the blocks -- contiguous slabs of the chain-major [C][S][D] layout -- are gathered into one
-// block on devices[0], one peer-to-peer copy per shard (hipMemcpyPeerAsync: over the shard's own xGMI link, all
-// inbound copies at once), and handed over as one wn_chains for the wn_summary_* functions.
-static int sample_multi_impl(const ResidentRequest* resident, WN_SAMPLE_PARAMS_NOERR, const int* devices,
-                             int num_devices, WalnutpyError** err) {
-  std::vector<wn_chains*> shard_chains(static_cast<size_t>(std::max(num_devices, 0)), nullptr);
-  struct ChainsGuard {
-    std::vector<wn_chains*>& v;
-    ~ChainsGuard() {
-      for (auto* c : v)
-        if (c != nullptr) wn_chains_destroy(c);
-    }
-  } chains_guard{shard_chains};
-  try {
-    if (devices == nullptr || num_devices < 1) throw std::invalid_argument("devices must name at least one device");
-    if (resident != nullptr) {
-      if (resident->chains_out == nullptr) throw std::invalid_argument("chains_out must not be null");
-      if (resident->thin < 0) throw std::invalid_argument("thin must be >= 0");
-      if (max_sampling_iter < 1) throw std::invalid_argument("resident draws need max_sampling_iter >= 1");
-      for (int d = 0; d < (resident->all_gather ? std::max(num_devices, 1) : 1); ++d) resident->chains_out[d] = nullptr;
-    }
-    if (num_chains < static_cast<size_t>(num_devices)) throw std::invalid_argument("fewer chains than devices");
-    if (num_params < 1) throw std::invalid_argument("num_params must be in {1, 2, ... }");
-    if (max_sampling_iter < 0 || max_warmup_iter < 0) throw std::invalid_argument("iteration counts must be >= 0");
-    int visible = 0;
-    if (hipGetDeviceCount(&visible) != hipSuccess) throw std::runtime_error("cannot count the devices");
-    for (int s = 0; s < num_devices; ++s)
-      if (devices[s] < 0 || devices[s] >= visible) throw std::invalid_argument("device ordinal out of range");
-    const size_t D = static_cast<size_t>(num_params);
-    // (the caller's rows per chain: every sampling draw, or -- resident -- only every thin-th of them)
-    const size_t thin = resident != nullptr ? static_cast<size_t>(resident->thin) : 1;
-    const size_t samp_rows = thin == 0 ? 0 : (static_cast<size_t>(max_sampling_iter) + thin - 1) / thin;
-    const size_t rows = samp_rows + (save_warmup ? static_cast<size_t>(max_warmup_iter) : 0);
-    if (rows > 0 && out == nullptr) throw std::invalid_argument("out must not be null");
-    if (out_size < num_chains * rows * D) {  // walnutpy.cpp:153-160
-      std::stringstream ss;
-      ss << "Output buffer too small. Expected at least " << num_chains << " chains of " << rows * D << " doubles, got "
-         << out_size;
-      throw std::runtime_error(ss.str());
-    }
-    InterruptGuard guard;
-    Coordinator coord(num_devices, D);
-    std::vector<WalnutpyError*> errors(static_cast<size_t>(num_devices), nullptr);
-    std::vector<int> rcs(static_cast<size_t>(num_devices), 0);
-    std::vector<std::thread> threads;
-    const size_t base = num_chains / static_cast<size_t>(num_devices), extra = num_chains % static_cast<size_t>(num_devices);
-    size_t begin = 0;
-    for (int s = 0; s < num_devices; ++s) {
-      const size_t count = base + (static_cast<size_t>(s) < extra ? 1 : 0);
-      ShardCtx ctx;
-      ctx.shard = s;
-      ctx.device = devices[s];
-      ctx.chain_begin = begin;
-      ctx.total_chains = num_chains;
-      ctx.coord = &coord;
-      ctx.interrupt = &guard;
-      ctx.lengths_warmup = final_lengths + begin;
-      ctx.lengths_sampling = final_lengths + num_chains + begin;
-      threads.emplace_back([&, ctx, count, s] {
-        const double* inits_s = inits == nullptr ? nullptr : inits + ctx.chain_begin * D;
-        const double* metric_s = init_inv_metric == nullptr ? nullptr : init_inv_metric + ctx.chain_begin * D;
-        double* out_s = out == nullptr ? nullptr : out + ctx.chain_begin * rows * D;
-        double* step_s = stepsize_out == nullptr ? nullptr : stepsize_out + ctx.chain_begin;
-        double* metric_out_s = inv_metric_out == nullptr ? nullptr : inv_metric_out + ctx.chain_begin * D;
-        const ResidentRequest shard_req{resident != nullptr ? resident->thin : 0, &shard_chains[static_cast<size_t>(s)]};
-        rcs[s] = sample_device_impl(
-            false, resident != nullptr ? &shard_req : nullptr, &ctx, nullptr, model, model_params, num_params, inits_s, count, seed, id, init_radius, metric_s,
-            min_warmup_iter, max_warmup_iter, min_sampling_iter, max_sampling_iter, max_trajectory_doublings,
-            max_step_halvings, min_micro_steps, max_hamiltonian_error, step_size_converge_tol, mass_converge_tol,
-            rhat_converge_tol, mass_init_count, mass_additive_smoothing, max_macro_steps_target, step_size_init,
-            step_accept_rate_target, step_learning_rate, step_gradient_decay, step_sq_gradient_decay,
-            step_stabilization, step_learn_rate_decay, save_warmup, out_s, count * rows * D, nullptr, step_s,
-            metric_out_s, refresh, print, &errors[s]);
-        if (rcs[s] != 0) coord.abandon();
-      });
-      begin += count;
-    }
-    for (auto& t : threads) t.join();
-    // the first shard that failed with an error of its own speaks for the call
-    int rc = 0;
-    for (int s = 0; s < num_devices; ++s) {
-      if (rcs[s] != 0 && errors[s] != nullptr && rc == 0) {
-        rc = -1;
-        if (err) *err = errors[s];
-        else walnutpie_destroy_error(errors[s]);
-        errors[s] = nullptr;
-      }
-    }
-    for (auto* e : errors)
-      if (e != nullptr) walnutpie_destroy_error(e);
-    if (rc == 0)
-      for (int s = 0; s < num_devices; ++s)
-        if (rcs[s] != 0) throw std::runtime_error("a shard ended without reporting its error");
-    if (rc == 0 && resident != nullptr) {
-      // gather: shard s's [count_s][S][D] block is rows [begin_s, begin_s + count_s) of the whole [C][S][D] block.
-      // One destination: devices[0] (gather), or every listed device (all_gather: the north star's exchange -- every
-      // device ends with every shard's draws).  Every (destination, source) pair is its own hipMemcpyPeerAsync on its
-      // own stream of the destination, so the inbound copies of a device run side by side, each over the xGMI link of
-      // its source -- not one after the other on one in-order stream.  Peer access is switched on per pair first: without
-      // it the runtime stages a peer copy through host memory.  (Unmeasured on more than one physical device: this pool
-      // has one GPU per box; the one-device tests list a device several times, where a "peer" copy is a local copy.)
-      const size_t S = static_cast<size_t>(max_sampling_iter);
-      struct RestoreDevice {  // the gather selects the destinations: the calling thread gets its current device back
-        int before = -1;
-        RestoreDevice() { if (hipGetDevice(&before) != hipSuccess) before = -1; }
-        ~RestoreDevice() { if (before >= 0) (void)hipSetDevice(before); }
-      } restore_device;
-      const int destinations = resident->all_gather ? num_devices : 1;
-      std::vector<size_t> first(static_cast<size_t>(num_devices) + 1, 0);
-      for (int s = 0; s < num_devices; ++s)
-        first[static_cast<size_t>(s) + 1] = first[static_cast<size_t>(s)] + wn_chains_num_chains(shard_chains[static_cast<size_t>(s)]);
-      std::vector<DevBlock> whole(static_cast<size_t>(destinations));
-      std::vector<std::unique_ptr<Stream>> copies;
-      for (int d = 0; d < destinations; ++d) {
-        const int dst = devices[d];
-        if (hipSetDevice(dst) != hipSuccess) throw std::runtime_error("cannot select the device");
-        if (!whole[static_cast<size_t>(d)].alloc(num_chains * S * D)) throw std::runtime_error("cannot allocate the gathered draw block");
-        for (int s = 0; s < num_devices; ++s) {
-          const int src = devices[s];
-          if (src != dst) {
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, dst, src) != hipSuccess || can == 0) {
-              std::stringstream ss;
-              ss << "device " << dst << " has no peer-to-peer path to device " << src
-                 << ": the shards' draws cannot be gathered on it (list devices of one xGMI hive)";
-              throw std::runtime_error(ss.str());
-            }
-            const hipError_t en = hipDeviceEnablePeerAccess(src, 0);
-            if (en != hipSuccess && en != hipErrorPeerAccessAlreadyEnabled) throw std::runtime_error("cannot enable peer access");
-            (void)hipGetLastError();  // (an "already enabled" is not an error to carry along)
-          }
-          copies.push_back(std::make_unique<Stream>());
-          copies.back()->create();
-          const size_t count = first[static_cast<size_t>(s) + 1] - first[static_cast<size_t>(s)];
-          if (hipMemcpyPeerAsync(whole[static_cast<size_t>(d)].p + first[static_cast<size_t>(s)] * S * D, dst,
-                                 wn_chains_device_draws(shard_chains[static_cast<size_t>(s)]), src,
-                                 count * S * D * sizeof(double), copies.back()->s) != hipSuccess)
-            throw std::runtime_error("gathering the shards' draws failed");
-        }
-      }
-      for (auto& c : copies)
-        if (hipStreamSynchronize(c->s) != hipSuccess) throw std::runtime_error("gathering the shards' draws failed");
-      std::vector<int64_t> lengths(num_chains);
-      for (size_t c = 0; c < num_chains; ++c) lengths[c] = final_lengths[num_chains + c];
-      for (int d = 0; d < destinations; ++d) resident->chains_out[d] = nullptr;
-      for (int d = 0; d < destinations; ++d) {
-        double* block = whole[static_cast<size_t>(d)].release();
-        WalnutpyError* adopt_err = nullptr;
-        if (wn_chains_adopt(&resident->chains_out[d], block, num_chains, S, D, static_cast<int64_t>(S * D), lengths.data(),
-                            devices[d], &adopt_err) != 0) {
-          (void)hipFree(block);
-          for (int k = 0; k < d; ++k) {  // (nothing half-built is handed back)
-            wn_chains_destroy(resident->chains_out[k]);
-            resident->chains_out[k] = nullptr;
-          }
-          rethrow(adopt_err);
-        }
-      }
-    }
-    return rc;
-  } catch (const std::invalid_argument& ex) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(ex.what(), config));
-  } catch (const std::exception& ex) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(ex.what(), generic));
-  } catch (...) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error("Unknown error", generic));
-  }
-  return -1;
-}
-#define WN_SAMPLE_ARGS_NOERR                                                                                       \
-  model, model_params, num_params, inits, num_chains, seed, id, init_radius, init_inv_metric, min_warmup_iter,     \
-      max_warmup_iter, min_sampling_iter, max_sampling_iter, max_trajectory_doublings, max_step_halvings,          \
-      min_micro_steps, max_hamiltonian_error, step_size_converge_tol, mass_converge_tol, rhat_converge_tol,        \
-      mass_init_count, mass_additive_smoothing, max_macro_steps_target, step_size_init, step_accept_rate_target,  \
-      step_learning_rate, step_gradient_decay, step_sq_gradient_decay, step_stabilization, step_learn_rate_decay, \
-      save_warmup, out, out_size, final_lengths, stepsize_out, inv_metric_out, refresh, print
-extern "C" int walnutpie_sample_device_multi(WN_SAMPLE_PARAMS_NOERR, const int* devices, int num_devices,
+extern "C" int walnutpie_sample_device_multi(int model, const double* model_params, int num_params,
+                                             WN_SAMPLE_ARG_LIST(WN_PARAM) const int* devices, int num_devices,
                                              WalnutpyError** err) {
-  return sample_multi_impl(nullptr, WN_SAMPLE_ARGS_NOERR, devices, num_devices, err);
+  return sample_multi({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, nullptr, devices, num_devices, err);
 }
-extern "C" int walnutpie_sample_device_multi_resident(WN_SAMPLE_PARAMS_NOERR, const int* devices, int num_devices, int thin,
-                                                      wn_chains** chains_out, WalnutpyError** err) {
+extern "C" int walnutpie_sample_device_multi_resident(int model, const double* model_params, int num_params,
+                                                      WN_SAMPLE_ARG_LIST(WN_PARAM) const int* devices, int num_devices,
+                                                      int thin, wn_chains** chains_out, WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out, false};
-  return sample_multi_impl(&req, WN_SAMPLE_ARGS_NOERR, devices, num_devices, err);
+  return sample_multi({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, &req, devices, num_devices, err);
 }
-extern "C" int walnutpie_sample_device_multi_allgather(WN_SAMPLE_PARAMS_NOERR, const int* devices, int num_devices, int thin,
-                                                       wn_chains** chains_out, WalnutpyError** err) {
+extern "C" int walnutpie_sample_device_multi_allgather(int model, const double* model_params, int num_params,
+                                                       WN_SAMPLE_ARG_LIST(WN_PARAM) const int* devices, int num_devices,
+                                                       int thin, wn_chains** chains_out, WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out, true};
-  return sample_multi_impl(&req, WN_SAMPLE_ARGS_NOERR, devices, num_devices, err);
+  return sample_multi({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, &req, devices, num_devices, err);
 }
 
 // ---- walnutpie_ess / walnutpie_r_hat / walnutpie_mcse (walnutpy.cpp:333-369) ----------------------------------
@@ -1488,14 +1453,9 @@ int summary_shim(const double* draws, int num_draws, int num_params, const int* 
     } guard{ch};
     WN_CALL(summarise(ch, out, &call_err_));
     return 0;
-  } catch (const std::invalid_argument& ex) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(ex.what(), config));
-  } catch (const std::exception& ex) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error(ex.what(), generic));
   } catch (...) {
-    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error("Unknown error", generic));
+    return report_exception(err);
   }
-  return -1;
 }
 }  // namespace
 
