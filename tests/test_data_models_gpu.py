@@ -3,7 +3,11 @@
   * device = emulation, bit for bit: the same kernel source under tests/cpusim and on gfx950, same geometry asked of both;
   * (1, 8) -- eight elements per lane, a geometry the emulation does not build -- against NumPy and for determinism;
   * the linear model against its closed-form posterior, the logistic model against its Laplace approximation;
-  * the drop-in call with data, draws on the host and kept on the device."""
+  * the drop-in call with data, draws on the host and kept on the device;
+  * the GLM edge matrix of test_data_models_sim.py (N around the block size, D at the padding boundary, saturated
+    logits) at 2, 4, 8 and 16 elements per lane against the high-precision reference;
+  * many chains (more than resident), fused transitions and two chain groups against emulated 8-chain slices at their
+    chain offsets, bit for bit: the data models have no oracle, so the emulation of the same source stands in for it."""
 import os
 import sys
 
@@ -15,7 +19,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "cpusim"))
 import build as simbuild  # noqa: E402
 import walnuts_amd as wa  # noqa: E402
-from test_data_models_sim import LIN, LOG, make_data, numpy_logp_grad  # noqa: E402
+from test_data_models_sim import LIN, LOG, check_glm_edges, edge_dims, make_data, numpy_logp_grad  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +46,8 @@ def run(lib, model, D, C, data, s2, geometry, fma, warm=6, samp=6):
 
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("model", [LIN, LOG])
-@pytest.mark.parametrize("D,N,geometry", [(5, 70, (1, 2)), (150, 130, (1, 4)), (1000, 60, (1, 16))])
+@pytest.mark.parametrize("D,N,geometry", [(5, 70, (1, 2)), (150, 130, (1, 4)), (1000, 60, (1, 16)),
+                                          (1000, 7, (1, 16)), (150, 5, (1, 4))])  # (odd N at B = 2; N < B = 8)
 @pytest.mark.parametrize("fma", [0, 1])
 def test_device_equals_emulation(gpu, model, D, N, geometry, fma):
     sim = simbuild.build()
@@ -171,3 +176,64 @@ def test_drop_in_call_with_data_on_the_device(gpu):
     assert np.allclose(chains.mean(), flat.mean(axis=0), rtol=1e-10, atol=1e-12)
     assert np.all(np.isfinite(chains.r_hat()))
     chains.close()
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("fma", [0, 1])
+@pytest.mark.parametrize("epl", [2, 4, 8, 16])
+@pytest.mark.parametrize("model", [LIN, LOG], ids=["linear", "logistic"])
+def test_glm_edges_on_the_device(gpu, model, epl, fma, record_property):
+    """The CPU tier's edge matrix on gfx950: N in 1, B - 1, B, B + 1 (and 7 at B = 2), D in 1, 64 EPL - 1, 64 EPL,
+    saturated and exactly-zero logits, all-zero and duplicated rows, y all 0 / all 1, |y| ~ 1e6."""
+    record_property("max_error_over_bound", max(check_glm_edges(None, model, epl, fma, D) for D in edge_dims(epl)))
+
+
+def sliced_run(lib, C, offset, mode, x, y, s2, wg_per_cu=0):
+    """logistic regression, C chains starting at chain `offset`: seed, init, adapt, then four warmup and four sampling
+    transitions -- one launch each ("single"), in launches of four ("fused"), both in one chain group, or in launches of
+    four split in two chain groups ("groups")."""
+    D = x.shape[1]
+    cfg = wa.default_config(lib, chain_groups=2 if mode == "groups" else 1, workgroups_per_cu=wg_per_cu)
+    e = wa.DeviceEngine(LOG, D, C, cfg, params=s2, lib_path=lib, data=(x, y))
+    if lib is None:
+        assert e.workgroups < C, "the device run must hold more chains than are resident"
+        assert e.chain_groups == (2 if mode == "groups" else 1)
+    e.seed_chains(7, offset)
+    e.init_positions(seed=3, chain_offset=offset, scale=0.5)
+    e.init_masses_from_grad(1e-5)
+    e.adapt_step(seed=4, chain_offset=offset)
+    if mode == "single":
+        for _ in range(4):
+            e.warmup_step()
+        e.freeze()
+        for _ in range(4):
+            e.sample_step()
+    else:
+        e.warmup_steps(4)
+        e.freeze()
+        e.sample_steps(4)
+    e.check()
+    out = dict(pos=e.positions(), logp=e.logp(), steps=e.step_sizes(), inv_mass=e.inv_mass(), depths=e.depths(),
+               grads=e.grad_evals())
+    e.close()
+    return out
+
+
+@pytest.mark.timeout(1800)
+def test_data_model_launches_against_emulated_slices(gpu):
+    """3 000 chains of logistic regression (D = 20, N = 37) on the device, one workgroup per CU so that chains queue
+    for the persistent workgroups, run as single transitions, fused launches and two chain groups: chains [0, 8),
+    [1496, 1504) and [2992, 3000) of every run equal emulation runs of 8 chains at those chain offsets, bit for bit."""
+    sim = simbuild.build()
+    D, N, C = 20, 37, 3000
+    rng = np.random.default_rng(1)
+    x = rng.normal(size=(N, D))
+    y = (rng.random(N) < 0.5).astype(np.float64)
+    s2 = np.full(D, 2.0)
+    slices = (0, 1496, 2992)
+    emu = {o: sliced_run(sim, 8, o, "single", x, y, s2) for o in slices}
+    for mode in ("single", "fused", "groups"):
+        dev = sliced_run(None, C, 0, mode, x, y, s2, wg_per_cu=1)
+        for o in slices:
+            for k in emu[o]:
+                assert np.array_equal(dev[k][o:o + 8], emu[o][k]), (mode, o, k)
