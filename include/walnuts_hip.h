@@ -175,6 +175,40 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_data_resident(
     int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
     int thin, wn_chains** chains_out, WalnutpyError** err);
 
+/* walnutpie_sample_device_data / _data_resident over MANY datasets at once (one model, one prior): dataset g is rows
+ * [obs_offsets[g], obs_offsets[g + 1]) of x and y (obs_offsets[num_datasets + 1], int64, from 0, strictly increasing;
+ * datasets may differ in size), and num_chains (the total) = num_datasets * k: chains [g * k, (g + 1) * k) are
+ * conditioned on dataset g.  Random streams stay keyed by the global chain id (the transition key is seed + id +
+ * num_chains), so dataset g's block of out / final_lengths / stepsize_out / inv_metric_out / the resident block is, bit
+ * for bit, what walnutpie_sample_device_data on dataset g alone would write for the same chain ids.  The stopping rules
+ * are per dataset, in lock step: warmup ends at the first look where EVERY dataset's spread meets both tolerances,
+ * sampling at the first R-hat look (only when k > 1) where every dataset's R-hat is at most rhat_converge_tol; the
+ * progress line prints the largest R-hat.  Outputs keep the layout of the calls above.  One device only. */
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_datasets(
+    int model, const double* model_params, int num_params, const double* x, const double* y, const int64_t* obs_offsets,
+    int num_datasets, const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    WalnutpyError** err);
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_datasets_resident(
+    int model, const double* model_params, int num_params, const double* x, const double* y, const int64_t* obs_offsets,
+    int num_datasets, const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    int thin, wn_chains** chains_out, WalnutpyError** err);
+
 /* walnutpie_sample_device over SEVERAL devices of the node ("one process, one driver thread +
  * stream per GPU").  devices[num_devices]: HIP ordinals; shard s -- a contiguous block of the global chain ids, sizes
  * differing by at most one -- runs on devices[s] with its own host thread, engine and stream and writes its own slice
@@ -330,6 +364,21 @@ WALNUTS_HIP_EXPORT int wn_engine_create(wn_engine** out, int model, int num_para
 WALNUTS_HIP_EXPORT int wn_engine_create_with_data(wn_engine** out, int model, int num_params, const double* model_params,
                                                   const double* x, const double* y, int num_obs, size_t num_chains,
                                                   const wn_config* cfg, WalnutpyError** err);
+/* MANY datasets of one data model in one engine (one prior, model_params shared): dataset g is rows
+ * [obs_offsets[g], obs_offsets[g + 1]) of x [rows][num_params] and y [rows] (obs_offsets[num_datasets + 1], int64,
+ * starting at 0, strictly increasing: sizes may differ), and chain c is conditioned on dataset c / k, k = num_chains /
+ * num_datasets (num_chains a multiple of num_datasets).  Random streams stay keyed by the chain id, so chain c of
+ * dataset g evolves bit for bit as chain c - g * k of an engine created with wn_engine_create_with_data on dataset g
+ * alone and seeded with chain_offset = g * k.  Config errors: num_datasets < 1, num_chains not a multiple of it,
+ * offsets not from 0 or not strictly increasing, non-finite data, a model without kUsesData, the model's own data
+ * checks failing for a dataset (the message names it), and the geometry rules of wn_engine_create_with_data.
+ * The pooled statistics below keep their meaning (all chains); the _datasets ones are per dataset. */
+WALNUTS_HIP_EXPORT int wn_engine_create_with_datasets(wn_engine** out, int model, int num_params,
+                                                      const double* model_params, const double* x, const double* y,
+                                                      const int64_t* obs_offsets, int num_datasets, size_t num_chains,
+                                                      const wn_config* cfg, WalnutpyError** err);
+/* datasets of an engine (1 for one created without wn_engine_create_with_datasets) */
+WALNUTS_HIP_EXPORT int wn_engine_num_datasets(const wn_engine* e);
 WALNUTS_HIP_EXPORT void wn_engine_destroy(wn_engine* e);
 /* The engine's model at positions the caller chooses: theta [C*D] in, logp_out [C] and grad_out [C*D] out (host
  * pointers), in the engine's arithmetic mode -- the reference's logp_grad(theta) -> (logp, grad) for every chain at
@@ -432,6 +481,15 @@ WALNUTS_HIP_EXPORT int wn_engine_lp_sums(wn_engine* e, double* out3, WalnutpyErr
 WALNUTS_HIP_EXPORT int wn_engine_lp_sq_dev(wn_engine* e, double mean_of_means, double* out1, WalnutpyError** err);
 WALNUTS_HIP_EXPORT int wn_engine_warmup_spread(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
                                                WalnutpyError** err);
+/* The same monitors per dataset of an engine from wn_engine_create_with_datasets (a config error on others): out
+ * arrays of num_datasets entries; entry g equals, bit for bit, what wn_engine_rhat / wn_engine_warmup_spread return on
+ * a standalone engine of dataset g's k chains in the same state.  wn_engine_average_masses_datasets: every chain's
+ * masses become the geometric mean over the chains of ITS dataset (wn_engine_average_masses keeps averaging over all
+ * chains). */
+WALNUTS_HIP_EXPORT int wn_engine_rhat_datasets(wn_engine* e, double* rhat /*[G]*/, WalnutpyError** err);
+WALNUTS_HIP_EXPORT int wn_engine_warmup_spread_datasets(wn_engine* e, double* max_rel_diff_step /*[G]*/,
+                                                        double* max_rel_diff_mass /*[G]*/, WalnutpyError** err);
+WALNUTS_HIP_EXPORT int wn_engine_average_masses_datasets(wn_engine* e, WalnutpyError** err);
 /* the same statistic in the two stages a multi-GPU driver all-reduces between: this engine's sums
  * over its chains of log step (1) and log mass ([D]) -> all-reduce SUM -> this engine's maxima given the sums over
  * all `total_chains` chains -> all-reduce MAX */

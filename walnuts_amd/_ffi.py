@@ -83,6 +83,15 @@ SYMBOLS = [
      [_i32, _dp, _i32, _dp, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
       _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
       C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
+    # ... and over several datasets: x, y, obs_offsets (int64 [G + 1]), num_datasets after num_params
+    ("walnutpie_sample_device_datasets", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32,
+      _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
+    ("walnutpie_sample_device_datasets_resident", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32,
+      _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
     ("walnutpie_sample_device_multi", _i32,
      [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
       _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
@@ -113,6 +122,9 @@ SYMBOLS = [
     ("wn_geometry_candidates", _i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int), _i32, C.POINTER(C.c_int), _errpp]),
     ("wn_engine_create", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _sz, C.POINTER(Config), _errpp]),
     ("wn_engine_create_with_data", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32, _sz, C.POINTER(Config), _errpp]),
+    ("wn_engine_create_with_datasets", _i32,
+     [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i64p, _i32, _sz, C.POINTER(Config), _errpp]),
+    ("wn_engine_num_datasets", _i32, [_vp]),
     ("wn_engine_destroy", None, [_vp]),
     ("wn_engine_eval", _i32, [_vp, _dp, _dp, _dp, _errpp]),
     ("wn_engine_set_positions", _i32, [_vp, _dp, _errpp]),
@@ -150,6 +162,9 @@ SYMBOLS = [
     ("wn_engine_lp_sums", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_lp_sq_dev", _i32, [_vp, _dbl, _dp, _errpp]),
     ("wn_engine_warmup_spread", _i32, [_vp, _dp, _dp, _errpp]),
+    ("wn_engine_rhat_datasets", _i32, [_vp, _dp, _errpp]),
+    ("wn_engine_warmup_spread_datasets", _i32, [_vp, _dp, _dp, _errpp]),
+    ("wn_engine_average_masses_datasets", _i32, [_vp, _errpp]),
     ("wn_engine_warmup_sums", _i32, [_vp, _dp, _dp, _errpp]),
     ("wn_engine_warmup_max_rel", _i32, [_vp, _dbl, _dp, _sz, _dp, _dp, _errpp]),
     ("wn_engine_lanes", _i32, [_vp]),

@@ -95,6 +95,9 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   static constexpr int kOther = -4;           // "this vector is the other end's theta" (kOtherRegs)
   Parked oth[EPL], orh[EPL];
   int n_lds;                                  // pool buffers [0, n_lds) live in LDS, the rest in the HBM arena
+  const double* obs_x = nullptr;              // data models: the bound chain's observations (bind_data)
+  const double* obs_yv = nullptr;
+  int obs_n = 0;
   int shift_parity = 0;                       // which copy of the shift scratch the last exchange used
 #if defined(WN_COUNT_POOL)
   int pool_count[4];
@@ -117,12 +120,31 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   // ---- model context (what Model::eval sees) ------------------------------------------------------
   __device__ __forceinline__ int index(int j) const { return ((j >> 1) * L + tid) * 2 + (j & 1); }
   __device__ __forceinline__ bool valid(int j) const { return index(j) < P.dim; }
-  // data models (wn_model_api.h, kUsesData): the engine's read-only observation block, rows laid out like theta
-  __device__ __forceinline__ int num_obs() const { return P.num_obs; }
+  // data models (wn_model_api.h, kUsesData): the chain's read-only observation block, rows laid out like theta --
+  // the engine's one block, or the chain's dataset of several (bind_data)
+  __device__ __forceinline__ int num_obs() const { return obs_n; }
   __device__ __forceinline__ void load_row(int n, double (&x)[EPL]) const {
-    vload(P.data_x + static_cast<long long>(n) * kDp, x);
+    vload(obs_x + static_cast<long long>(n) * kDp, x);
   }
-  __device__ __forceinline__ double obs_y(int n) const { return P.data_y[n]; }
+  __device__ __forceinline__ double obs_y(int n) const { return obs_yv[n]; }
+  // Once per chain, before the model is evaluated for it: chain c of an engine with several datasets reads dataset
+  // c / chains_per_dataset (the chain index is wave-uniform: one division and two scalar loads per chain, none per
+  // row).  Row offsets are 64-bit, so a block beyond 4 GiB is addressed correctly.
+  __device__ __forceinline__ void bind_data(int c) {
+    if constexpr (uses_data<Model>::value) {
+      if (P.chains_per_dataset > 0) {
+        const int ds = c / P.chains_per_dataset;
+        const long long first = P.data_offsets[ds];
+        obs_x = P.data_x + first * kDp;
+        obs_yv = P.data_y + first;
+        obs_n = static_cast<int>(P.data_offsets[ds + 1] - first);
+      } else {
+        obs_x = P.data_x;
+        obs_yv = P.data_y;
+        obs_n = P.num_obs;
+      }
+    }
+  }
   template <int S>
   __device__ __forceinline__ double G(int j) const {
     return kNoGrad ? Model::grad_elem(th[S][j], mp[j]) : g[S][j];
@@ -597,6 +619,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
     pool_count[0] = pool_count[1] = pool_count[2] = pool_count[3] = 0;
 #endif
     chain = chain_id;
+    bind_data(chain);
     err = 0;
     n_grad = 0;
     n_draw = 0;

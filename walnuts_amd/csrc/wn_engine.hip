@@ -64,6 +64,14 @@ struct wn_engine {
   DevBuf<double> lp_stats, mon_partial, mon_out, mon_colsum, mon_rel_mass, mon_rel_step;
   DevBuf<double> data_x, data_y;  // a data model's observations: [num_obs][Dp] (rows padded with zeros), [num_obs]
   int num_obs = 0;
+  // several datasets (wn_engine_create_with_datasets): data_x / data_y hold them one after another, dataset g being rows
+  // [data_offsets[g], data_offsets[g + 1]) and chains [g * k, (g + 1) * k), k = chains_per_dataset; 0 = one shared block
+  DevBuf<int64_t> data_offsets;
+  int num_datasets = 1;
+  int chains_per_dataset = 0;
+  // the per-dataset monitors' buffers (allocated with the datasets): run partials, [G][2] sums, [G] second-stage sums,
+  // [G][D] column sums, [G][2] maxima
+  DevBuf<double> ds_partial, ds_sums, ds_q, ds_colsum, ds_max;
   DevBuf<int32_t> min_micro, depth, rng_draws, failed_ext;
   DevBuf<int64_t> grad_evals;
   DevBuf<uint32_t> counter, error_flags;
@@ -278,6 +286,8 @@ struct wn_engine {
     P.data_y = data_y.p;
     P.num_obs = num_obs;
     P.data_stride = Dp;
+    P.data_offsets = data_offsets.p;
+    P.chains_per_dataset = chains_per_dataset;
     return P;
   }
 
@@ -417,9 +427,11 @@ int required_pool(const wn_config& c) {
 
 // a data model's observations as the caller hands them over (host memory, row-major; not retained)
 struct HostData {
-  const double* x;  // [num_obs][num_params]
+  const double* x;  // [num_obs][num_params] -- or, with offsets, [offsets[num_datasets]][num_params]
   const double* y;  // [num_obs]
   int num_obs;
+  const int64_t* offsets = nullptr;  // several datasets: dataset g is rows [offsets[g], offsets[g + 1])
+  int num_datasets = 0;              // 0: one block shared by every chain
 };
 
 void build_engine(wn_engine& e, int model, int num_params, const double* model_params, size_t num_chains,
@@ -443,15 +455,45 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
                                 "wn_engine_create_with_data (x [num_obs][num_params], y [num_obs])");
   if (!ops.uses_data && data != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
-  if (data != nullptr) {
+  size_t total_obs = 0;  // rows of the observation block
+  if (data != nullptr && data->offsets != nullptr) {
+    const int G = data->num_datasets;
+    if (G < 1) throw std::invalid_argument("num_datasets must be positive");
+    if (num_chains % static_cast<size_t>(G) != 0)
+      throw std::invalid_argument("num_chains must be a multiple of num_datasets (chain c reads dataset c / (num_chains / "
+                                  "num_datasets))");
+    if (data->offsets[0] != 0) throw std::invalid_argument("obs_offsets must start at 0");
+    for (int g = 0; g < G; ++g) {
+      const int64_t n = data->offsets[g + 1] - data->offsets[g];
+      if (n < 1)
+        throw std::invalid_argument("obs_offsets must be strictly increasing (every dataset needs at least one observation)");
+      if (n > INT32_MAX) throw std::invalid_argument("a dataset holds more than 2^31 - 1 observations");
+    }
+    total_obs = static_cast<size_t>(data->offsets[G]);
+  } else if (data != nullptr) {
     if (data->num_obs < 1) throw std::invalid_argument("num_obs must be positive");
+    total_obs = static_cast<size_t>(data->num_obs);
+  }
+  if (data != nullptr) {
     if (data->x == nullptr || data->y == nullptr) throw std::invalid_argument("null data argument");
-    const size_t n = static_cast<size_t>(data->num_obs) * static_cast<size_t>(num_params);
+    const size_t n = total_obs * static_cast<size_t>(num_params);
     for (size_t i = 0; i < n; ++i)
       if (!std::isfinite(data->x[i])) throw std::invalid_argument("data x must be finite");
-    for (int i = 0; i < data->num_obs; ++i)
+    for (size_t i = 0; i < total_obs; ++i)
       if (!std::isfinite(data->y[i])) throw std::invalid_argument("data y must be finite");
-    ops.host_data(data->x, data->y, data->num_obs, num_params);
+    if (data->offsets == nullptr) {
+      ops.host_data(data->x, data->y, data->num_obs, num_params);
+    } else {
+      for (int g = 0; g < data->num_datasets; ++g) {
+        const int64_t first = data->offsets[g];
+        try {
+          ops.host_data(data->x + static_cast<size_t>(first) * num_params, data->y + first,
+                        static_cast<int>(data->offsets[g + 1] - first), num_params);
+        } catch (const std::invalid_argument& ex) {
+          throw std::invalid_argument("dataset " + std::to_string(g) + ": " + ex.what());
+        }
+      }
+    }
   }
 
   e.model = model;
@@ -599,7 +641,7 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     HIP_OK(hipMemcpyAsync(e.model_params.p, mp.data(), mp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
     HIP_OK(hipStreamSynchronize(e.stream));
   }
-  if (data != nullptr) {
+  if (data != nullptr && data->offsets == nullptr) {
     // rows padded to Dp with zeros: the layout of a theta row (lane tid's slot j holds coordinate index(j))
     const size_t N = static_cast<size_t>(data->num_obs);
     std::vector<double> xp(N * static_cast<size_t>(e.Dp), 0.0);
@@ -609,6 +651,36 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     e.num_obs = data->num_obs;
     HIP_OK(hipMemcpyAsync(e.data_x.p, xp.data(), xp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
     HIP_OK(hipMemcpyAsync(e.data_y.p, data->y, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
+    HIP_OK(hipStreamSynchronize(e.stream));
+  } else if (data != nullptr) {
+    // the datasets one after another, rows padded as above; the padded copy goes up in slices of at most 64 MiB (a
+    // block of many datasets may be larger than what is sensible to double in host memory)
+    const size_t N = total_obs, Dp = static_cast<size_t>(e.Dp);
+    const int G = data->num_datasets;
+    e.data_x.alloc(N * Dp);
+    e.data_y.alloc(N);
+    e.data_offsets.alloc(static_cast<size_t>(G) + 1);
+    e.num_obs = 0;  // (per dataset: data_offsets)
+    e.num_datasets = G;
+    e.chains_per_dataset = static_cast<int>(num_chains / static_cast<size_t>(G));
+    const size_t slice = std::max<size_t>(1, (size_t{64} << 20) / (Dp * sizeof(double)));
+    std::vector<double> xp(std::min(N, slice) * Dp, 0.0);
+    for (size_t n0 = 0; n0 < N; n0 += slice) {
+      const size_t rows = std::min(slice, N - n0);
+      for (size_t n = 0; n < rows; ++n)
+        std::memcpy(&xp[n * Dp], data->x + (n0 + n) * num_params, sizeof(double) * num_params);
+      HIP_OK(hipMemcpyAsync(e.data_x.p + n0 * Dp, xp.data(), rows * Dp * sizeof(double), hipMemcpyHostToDevice, e.stream));
+      HIP_OK(hipStreamSynchronize(e.stream));  // (before the staging slice is refilled)
+    }
+    HIP_OK(hipMemcpyAsync(e.data_y.p, data->y, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
+    HIP_OK(hipMemcpyAsync(e.data_offsets.p, data->offsets, (static_cast<size_t>(G) + 1) * sizeof(int64_t),
+                          hipMemcpyHostToDevice, e.stream));
+    const size_t k = static_cast<size_t>(e.chains_per_dataset);
+    e.ds_partial.alloc(2 * static_cast<size_t>(G) * static_cast<size_t>(wn::monitor_runs(static_cast<int>(k))));
+    e.ds_sums.alloc(2 * static_cast<size_t>(G));
+    e.ds_q.alloc(static_cast<size_t>(G));
+    e.ds_colsum.alloc(static_cast<size_t>(G) * static_cast<size_t>(num_params));
+    e.ds_max.alloc(2 * static_cast<size_t>(G));
     HIP_OK(hipStreamSynchronize(e.stream));
   }
   wn::prepare_kernels(model, e.geo, e.smem);
@@ -642,6 +714,8 @@ void run_init(wn_engine& e, bool pos, bool masses, bool step, double scale, doub
   Q.data_y = e.data_y.p;
   Q.num_obs = e.num_obs;
   Q.data_stride = e.Dp;
+  Q.data_offsets = e.data_offsets.p;
+  Q.chains_per_dataset = e.chains_per_dataset;
   const int grid = e.geo.mem ? e.grid : static_cast<int>(std::min<size_t>(e.C, static_cast<size_t>(e.num_cus) * 8));
   wn::launch_init(e.model, e.geo, grid, wn::transition_smem_bytes(e.geo.nw, 0, e.Dp), e.stream, Q);
   HIP_OK(hipGetLastError());
@@ -821,6 +895,20 @@ int wn_engine_create_with_data(wn_engine** out, int model, int num_params, const
     *out = e.release();
   });
 }
+int wn_engine_create_with_datasets(wn_engine** out, int model, int num_params, const double* model_params,
+                                   const double* x, const double* y, const int64_t* obs_offsets, int num_datasets,
+                                   size_t num_chains, const wn_config* cfg, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (out == nullptr || cfg == nullptr || obs_offsets == nullptr) throw std::invalid_argument("null argument");
+    HostData data{x, y, 0};
+    data.offsets = obs_offsets;
+    data.num_datasets = num_datasets;
+    auto e = std::make_unique<wn_engine>();
+    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
+    *out = e.release();
+  });
+}
+int wn_engine_num_datasets(const wn_engine* e) { return e->num_datasets; }
 void wn_engine_destroy(wn_engine* e) { delete e; }
 
 int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* grad_out, WalnutpyError** err) {
@@ -849,6 +937,8 @@ int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* 
     Q.data_y = e->data_y.p;
     Q.num_obs = e->num_obs;
     Q.data_stride = e->Dp;
+    Q.data_offsets = e->data_offsets.p;
+    Q.chains_per_dataset = e->chains_per_dataset;
     Q.logp_out = lp.p;
     Q.grad_out = grad.p;
     const int grid = e->geo.mem ? e->grid : static_cast<int>(std::min<size_t>(C, static_cast<size_t>(e->num_cus) * 8));
@@ -1228,6 +1318,91 @@ int wn_engine_warmup_spread(wn_engine* e, double* max_rel_diff_step, double* max
       delete inner;
       throw std::runtime_error(msg);
     }
+  });
+}
+
+// ---- the same monitors per dataset (wn_engine_create_with_datasets) ---------------------------------------------------
+// Dataset g's value is, bit for bit, what wn_engine_rhat / wn_engine_warmup_spread / wn_engine_average_masses return on a
+// standalone engine of its k chains: the kernels of wn_elementwise.h (*_ds_kernel) keep the pooled kernels' order within
+// each dataset, and each stage is one launch whatever the number of datasets.  On an engine with one shared data block
+// (or none) the one "dataset" is all chains.
+namespace {
+void require_datasets(const wn_engine* e) {
+  if (e->chains_per_dataset == 0)
+    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_with_datasets)");
+}
+int ds_grid(size_t n) { return static_cast<int>(std::max<size_t>(1, (n + 255) / 256)); }
+}  // namespace
+
+int wn_engine_rhat_datasets(wn_engine* e, double* rhat, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (rhat == nullptr) throw std::invalid_argument("null argument");
+    require_datasets(e);
+    e->use_device();
+    const int G = e->num_datasets, k = e->chains_per_dataset, per = wn::monitor_runs(k);
+    const size_t runs = static_cast<size_t>(G) * per;
+    hipLaunchKernelGGL(wn::lp_sums_ds_kernel, dim3(ds_grid(runs)), dim3(256), 0, e->stream, G, k, e->lp_stats.p,
+                       e->ds_partial.p);
+    hipLaunchKernelGGL(wn::finish_sums_ds_kernel<2>, dim3(ds_grid(G)), dim3(256), 0, e->stream, e->ds_partial.p, G, per,
+                       e->ds_sums.p);
+    hipLaunchKernelGGL(wn::lp_sqdev_ds_kernel, dim3(ds_grid(runs)), dim3(256), 0, e->stream, G, k, e->lp_stats.p,
+                       e->ds_sums.p, e->ds_partial.p);
+    hipLaunchKernelGGL(wn::finish_sums_ds_kernel<1>, dim3(ds_grid(G)), dim3(256), 0, e->stream, e->ds_partial.p, G, per,
+                       e->ds_q.p);
+    HIP_OK(hipGetLastError());
+    std::vector<double> s(2 * static_cast<size_t>(G)), q(static_cast<size_t>(G));
+    e->download(e->ds_sums, s.data(), s.size());
+    e->download(e->ds_q, q.data(), q.size());
+    const double n = static_cast<double>(k);
+    for (int g = 0; g < G; ++g) {  // wn_engine_rhat's arithmetic
+      const double variance_of_means = q[g] / (n - 1);
+      const double mean_of_variances = s[2 * g + 1] / n;
+      rhat[g] = std::sqrt(1 + variance_of_means / mean_of_variances);
+    }
+  });
+}
+int wn_engine_warmup_spread_datasets(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
+                                     WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (max_rel_diff_step == nullptr || max_rel_diff_mass == nullptr) throw std::invalid_argument("null argument");
+    require_datasets(e);
+    if (e->frozen) throw std::runtime_error("warmup monitor after freeze");
+    e->ensure_adapters();
+    e->use_device();
+    const int G = e->num_datasets, k = e->chains_per_dataset, per = wn::monitor_runs(k), C = static_cast<int>(e->C);
+    const size_t runs = static_cast<size_t>(G) * per;
+    hipLaunchKernelGGL(wn::log_step_sum_ds_kernel, dim3(ds_grid(runs)), dim3(256), 0, e->stream, G, k, e->adam.p,
+                       e->ds_partial.p);
+    hipLaunchKernelGGL(wn::finish_sums_ds_kernel<1>, dim3(ds_grid(G)), dim3(256), 0, e->stream, e->ds_partial.p, G, per,
+                       e->ds_q.p);
+    hipLaunchKernelGGL(wn::log_mass_colsum_ds_kernel, dim3(ds_grid(static_cast<size_t>(G) * e->D)), dim3(256), 0,
+                       e->stream, G, k, e->D, e->Dp, e->draw_ssd.p, e->score_ssd.p, e->est_weight.p, e->ds_colsum.p);
+    hipLaunchKernelGGL(wn::warmup_spread_ds_kernel, dim3(C), dim3(256), 0, e->stream, k, e->D, e->Dp, e->draw_ssd.p,
+                       e->score_ssd.p, e->est_weight.p, e->adam.p, e->ds_colsum.p, e->ds_q.p, e->mon_rel_mass.p,
+                       e->mon_rel_step.p);
+    hipLaunchKernelGGL(wn::max2_ds_kernel, dim3(G), dim3(256), 0, e->stream, k, e->mon_rel_mass.p, e->mon_rel_step.p,
+                       e->ds_max.p);
+    HIP_OK(hipGetLastError());
+    std::vector<double> m(2 * static_cast<size_t>(G));
+    e->download(e->ds_max, m.data(), m.size());
+    for (int g = 0; g < G; ++g) {
+      max_rel_diff_mass[g] = m[2 * g];
+      max_rel_diff_step[g] = m[2 * g + 1];
+    }
+  });
+}
+int wn_engine_average_masses_datasets(wn_engine* e, WalnutpyError** err) {
+  return guarded(err, [&] {
+    require_datasets(e);
+    e->use_device();
+    const int G = e->num_datasets, k = e->chains_per_dataset, C = static_cast<int>(e->C);
+    hipLaunchKernelGGL(wn::mass_log_colsum_ds_kernel, dim3(ds_grid(static_cast<size_t>(G) * e->D)), dim3(256), 0,
+                       e->stream, G, k, e->D, e->Dp, e->mass.p, e->ds_colsum.p);
+    const int blocks = static_cast<int>(std::min<size_t>((e->C * e->Dp + 255) / 256, 4096));
+    hipLaunchKernelGGL(wn::mass_broadcast_ds_kernel, dim3(blocks), dim3(256), 0, e->stream, C, k, e->D, e->Dp,
+                       e->ds_colsum.p, e->mass.p);
+    HIP_OK(hipGetLastError());
+    e->adapters_ready = false;
   });
 }
 

@@ -29,6 +29,8 @@ struct InitParams {
   const double* data_y;
   int32_t num_obs;
   int32_t data_stride;
+  const int64_t* data_offsets;
+  int32_t chains_per_dataset;
   // eval_kernel (wn_engine_eval): the model's log density [C] and gradient [C][Dp] at theta
   double* logp_out;
   double* grad_out;
@@ -47,6 +49,8 @@ __global__ __launch_bounds__(64 * NW) void init_kernel(const InitParams Q) {
   P.data_y = Q.data_y;
   P.num_obs = Q.num_obs;
   P.data_stride = Q.data_stride;
+  P.data_offsets = Q.data_offsets;
+  P.chains_per_dataset = Q.chains_per_dataset;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;
@@ -57,6 +61,7 @@ __global__ __launch_bounds__(64 * NW) void init_kernel(const InitParams Q) {
 
   for (int chain = blockIdx.x; chain < Q.num_chains; chain += gridDim.x) {
     const long long row = static_cast<long long>(chain) * Q.dim_padded;
+    t.bind_data(chain);
     t.n_grad = 0;
     if (Model::kUsesParams) t.vload(Q.model_params, t.mp);
     if (Q.do_positions) {
@@ -154,6 +159,8 @@ __global__ __launch_bounds__(64 * NW) void eval_kernel(const InitParams Q) {
   P.data_y = Q.data_y;
   P.num_obs = Q.num_obs;
   P.data_stride = Q.data_stride;
+  P.data_offsets = Q.data_offsets;
+  P.chains_per_dataset = Q.chains_per_dataset;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;
@@ -161,6 +168,7 @@ __global__ __launch_bounds__(64 * NW) void eval_kernel(const InitParams Q) {
   T t(P, base, meta, red, bcast, nullptr);
   for (int chain = blockIdx.x; chain < Q.num_chains; chain += gridDim.x) {
     const long long row = static_cast<long long>(chain) * Q.dim_padded;
+    t.bind_data(chain);
     if (Model::kUsesParams) t.vload(Q.model_params, t.mp);
     t.vload(Q.theta + row, t.th[0]);
 #pragma unroll

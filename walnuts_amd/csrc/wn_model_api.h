@@ -73,7 +73,9 @@
 //   cx.gather_tab()                           the same tables for a per-lane argument (every lane takes part)
 //   Cx::mad(a, b, c)                          a * b + c: one fused multiply-add when the engine was created with
 //                                             wn_config::fused_multiply_add, a rounded product plus an add otherwise
-// ... and, compiled in for data models only (kUsesData; one wavefront per chain, so Cx::L == 64):
+// ... and, compiled in for data models only (kUsesData; one wavefront per chain, so Cx::L == 64).  They are relative to
+// the CHAIN's dataset: the engine's one block, or -- an engine built with several datasets
+// (wn_engine_create_with_datasets) -- the block of the dataset the chain is conditioned on; the model cannot tell:
 //   cx.num_obs()                              number of observations, wave-uniform
 //   cx.load_row(n, x)                         double x[EPL] = the lane's slots of row n of x: slot j holds column
 //                                             cx.index(j), zero beyond num_params (a row is laid out like theta and

@@ -98,6 +98,10 @@ struct Params {
   const double* data_y;  // [num_obs]
   int32_t num_obs;
   int32_t data_stride;
+  // several datasets (wn_engine_create_with_datasets): chain c reads dataset c / chains_per_dataset, rows
+  // [data_offsets[g], data_offsets[g + 1]) of data_x / data_y; chains_per_dataset = 0: one block shared by every chain
+  const int64_t* data_offsets;  // [G + 1]
+  int32_t chains_per_dataset;
 };
 
 enum : uint32_t {

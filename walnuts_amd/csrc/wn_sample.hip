@@ -688,7 +688,11 @@ namespace {
 struct ShardAborted {};  // another shard failed: leave quietly, the wrapper reports that shard's error
 class Coordinator {
  public:
-  Coordinator(int shards, size_t dims) : n_(shards), D_(dims), slots_(static_cast<size_t>(shards) * (dims + 4), 0.0) {}
+  // datasets > 0: one shard whose engine holds that many datasets (wn_engine_create_with_datasets); each statistic is
+  // then taken per dataset and every dataset has to meet the rule
+  Coordinator(int shards, size_t dims, int datasets = 0)
+      : n_(shards), D_(dims), G_(datasets), slots_(static_cast<size_t>(shards) * (dims + 4), 0.0) {}
+  int datasets() const { return G_ > 0 ? G_ : 1; }
   // a failing shard stops taking part; the others notice at their next rendezvous
   void abandon() {
     std::lock_guard<std::mutex> lk(mu_);
@@ -699,6 +703,13 @@ class Coordinator {
   }
   // adapt.hpp:193-221 over ALL shards' chains
   bool warmup_converged(int shard, wn_engine* e, size_t total_chains, double step_tol, double mass_tol) {
+    if (G_ > 0) {  // every dataset's spread (wn_engine_warmup_spread over its chains) meets both tolerances
+      std::vector<double> step(static_cast<size_t>(G_)), mass(static_cast<size_t>(G_));
+      WN_CALL(wn_engine_warmup_spread_datasets(e, step.data(), mass.data(), &call_err_));
+      for (int g = 0; g < G_; ++g)
+        if (!(mass[g] <= mass_tol && step[g] <= step_tol)) return false;
+      return true;
+    }
     std::vector<double> sums(D_ + 1);  // sum of log step sizes, column sums of log masses
     WN_CALL(wn_engine_warmup_sums(e, sums.data(), sums.data() + 1, &call_err_));
     all_reduce(shard, sums.data(), D_ + 1, [](double x, double y) { return x + y; });
@@ -708,7 +719,16 @@ class Coordinator {
     return rel[1] <= mass_tol && rel[0] <= step_tol;
   }
   // sampler.hpp:139-145 over ALL shards' chains
+  // (several datasets: the largest of their R-hats, NaN if any is -- at most the tolerance exactly when every one is)
   double rhat(int shard, wn_engine* e) {
+    if (G_ > 0) {
+      std::vector<double> r(static_cast<size_t>(G_));
+      WN_CALL(wn_engine_rhat_datasets(e, r.data(), &call_err_));
+      double m = r[0];
+      for (int g = 1; g < G_ && !std::isnan(m); ++g)
+        if (!(r[g] <= m)) m = r[g];
+      return m;
+    }
     const auto sum = [](double x, double y) { return x + y; };
     double s[3];  // sum of means, sum of sample variances, chains
     WN_CALL(wn_engine_lp_sums(e, s, &call_err_));
@@ -752,6 +772,7 @@ class Coordinator {
   int n_;
   const int total_shards_ = n_;
   size_t D_;
+  int G_;
   std::vector<double> slots_;
   std::mutex mu_;
   std::condition_variable cv_;
@@ -815,11 +836,15 @@ struct ResidentRequest {  // walnutpie_sample_device*_resident, _multi_allgather
   wn_chains** chains_out;
   bool all_gather = false;  // multi-device: chains_out is an array of num_devices handles, every device gets the whole block
 };
-// a data model's observations (walnutpie_sample_device_data*): host pointers, copied by wn_engine_create_with_data
+// a data model's observations (walnutpie_sample_device_data*): host pointers, copied by wn_engine_create_with_data --
+// or, walnutpie_sample_device_datasets*, several datasets one after another, copied by wn_engine_create_with_datasets
 struct SampleData {
   const double* x;  // [num_obs][num_params]
   const double* y;  // [num_obs]
   int num_obs;
+  bool several = false;              // walnutpie_sample_device_datasets*: the two fields below describe the datasets
+  const int64_t* offsets = nullptr;  // dataset g is rows [offsets[g], offsets[g + 1])
+  int num_datasets = 0;
 };
 struct Mode {
   bool reference_streams = false;            // walnutpie_sample_device_reference_streams
@@ -1067,7 +1092,7 @@ struct Iterations {
     }
   }
   bool controller_looks_after(int it) const {
-    return it >= a.min_sampling_iter && it >= 2 && it < a.max_sampling_iter && shard.total_chains > 1 &&
+    return it >= a.min_sampling_iter && it >= 2 && it < a.max_sampling_iter && shard.total_chains / coord.datasets() > 1 &&
            (it - a.min_sampling_iter) % rhat_stride == 0;
   }
   static constexpr int rhat_stride = 5;
@@ -1085,7 +1110,10 @@ void run_shard(const Model& m, const SampleArgs& a, const Mode& mode, const Plan
   // started once the device allocations are done -- see below)
   std::unique_ptr<Prefault> populate;
   EngineGuard guard;
-  if (mode.data != nullptr) {
+  if (mode.data != nullptr && mode.data->several) {
+    WN_CALL(wn_engine_create_with_datasets(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
+                                           mode.data->offsets, mode.data->num_datasets, C, &plan.cfg, &call_err_));
+  } else if (mode.data != nullptr) {
     WN_CALL(wn_engine_create_with_data(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
                                        mode.data->num_obs, C, &plan.cfg, &call_err_));
   } else {
@@ -1177,7 +1205,8 @@ void run_shard(const Model& m, const SampleArgs& a, const Mode& mode, const Plan
 int sample_one(const Model& m, const SampleArgs& a, const Mode& mode, WalnutpyError** err) {
   try {
     const Plan plan = validate(m, a, mode);
-    Coordinator one(1, static_cast<size_t>(m.num_params));
+    Coordinator one(1, static_cast<size_t>(m.num_params),
+                    mode.data != nullptr && mode.data->several ? mode.data->num_datasets : 0);
     run_shard(m, a, mode, plan, Shard{0, 0, a.num_chains, a.final_lengths, a.final_lengths + a.num_chains, nullptr}, one);
     return 0;
   } catch (...) {
@@ -1401,6 +1430,21 @@ extern "C" int walnutpie_sample_device_data_resident(int model, const double* mo
                                                      WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out};
   const SampleData data{x, y, num_obs};
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
+}
+// ... and for several datasets (obs_offsets, num_datasets after y): chains [g * k, (g + 1) * k) on dataset g
+extern "C" int walnutpie_sample_device_datasets(int model, const double* model_params, int num_params, const double* x,
+                                                const double* y, const int64_t* obs_offsets, int num_datasets,
+                                                WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
+  const SampleData data{x, y, 0, true, obs_offsets, num_datasets};
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
+}
+extern "C" int walnutpie_sample_device_datasets_resident(int model, const double* model_params, int num_params,
+                                                         const double* x, const double* y, const int64_t* obs_offsets,
+                                                         int num_datasets, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
+                                                         wn_chains** chains_out, WalnutpyError** err) {
+  const ResidentRequest req{thin, chains_out};
+  const SampleData data{x, y, 0, true, obs_offsets, num_datasets};
   return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
 }
 extern "C" int walnutpie_sample_device_multi(int model, const double* model_params, int num_params,

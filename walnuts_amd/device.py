@@ -137,6 +137,7 @@ def walnuts_device(
     lib_path: Optional[str] = None,
     print_callback=None,
     data=None,
+    datasets=None,
 ):
     """The device-model sibling of the reference's ``walnuts_pyfunc`` (pyfunc.py:45-286): same keywords, same result
     (a list of per-chain draw arrays carrying ``.warmup``).
@@ -159,8 +160,21 @@ def walnuts_device(
     ``data=(x, y)`` (walnutpie_sample_device_data / _data_resident): the observations of a model conditioned on data
     (``MODEL_LINEAR_REGRESSION``, ``MODEL_LOGISTIC_REGRESSION`` or a model of your own that declares ``kUsesData``),
     ``x`` of shape (num_obs, num_params) and ``y`` of shape (num_obs,); copied to the device once.  One device only:
-    not with ``devices`` or ``reference_streams``."""
+    not with ``devices`` or ``reference_streams``.
+
+    ``datasets=[(x0, y0), (x1, y1), ...]`` (walnutpie_sample_device_datasets / _datasets_resident): G datasets of the
+    same model and prior, fitted in one run.  ``num_chains`` (the total) must be a multiple k of G; chains
+    [g*k, (g+1)*k) are conditioned on dataset g, and the results list is per chain as usual.  Warmup and sampling stop
+    when EVERY dataset meets the rules (spread per dataset, R-hat per dataset).  With ``keep_on_device=True`` the call
+    returns ``(results, [MarkovChains of dataset 0, of dataset 1, ...])``: views into one device block that stays alive
+    while any of them does.  Not with ``data``, ``devices`` or ``reference_streams``."""
     lib = _ffi.load_library(lib_path)
+    if data is not None and datasets is not None:
+        raise ValueError("data and datasets are mutually exclusive")
+    if datasets is not None and devices is not None:
+        raise ValueError("datasets is not available with devices (data models run on one device)")
+    if datasets is not None and reference_streams:
+        raise ValueError("datasets is not available with reference_streams")
     if data is not None and devices is not None:
         raise ValueError("data is not available with devices (data models run on one device)")
     if data is not None and reference_streams:
@@ -194,6 +208,14 @@ def walnuts_device(
 
         x, y = _data_arrays(data, num_params)
         data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), y.size)
+    num_datasets = 1
+    if datasets is not None:
+        from .engine import _datasets_arrays
+
+        x, y, offsets = _datasets_arrays(datasets, num_params)
+        num_datasets = offsets.size - 1
+        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), offsets.ctypes.data_as(_ffi._i64p),
+                     num_datasets)
     mp = None if model_params is None else np.ascontiguousarray(np.asarray(model_params, dtype=np.float64))
     if mp is not None and mp.size != num_params:
         raise ValueError("model_params must have num_params entries")
@@ -229,6 +251,8 @@ def walnuts_device(
         tail = (refresh, cb, thin, C.byref(chains_handle), C.byref(err))
     if data is not None:
         entry = lib.walnutpie_sample_device_data_resident if keep_on_device else lib.walnutpie_sample_device_data
+    if datasets is not None:
+        entry = lib.walnutpie_sample_device_datasets_resident if keep_on_device else lib.walnutpie_sample_device_datasets
     if devices is not None:
         dev = (C.c_int * len(devices))(*[int(d) for d in devices])
         entry = lib.walnutpie_sample_device_multi
@@ -281,5 +305,9 @@ def walnuts_device(
 
         if all_gather and devices is not None:
             return results, [MarkovChains(C.c_void_p(h), lib) for h in handles]
-        return results, MarkovChains(chains_handle, lib)
+        chains = MarkovChains(chains_handle, lib)
+        if datasets is not None:   # one view per dataset's block of chains
+            lengths = final_lengths[num_chains:].astype(np.int64)
+            return results, chains.chain_blocks(num_datasets, max_sampling_iter, lengths)
+        return results, chains
     return results

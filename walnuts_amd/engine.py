@@ -63,11 +63,35 @@ def _data_arrays(data, num_params: int):
     return x, y
 
 
+def _datasets_arrays(datasets, num_params: int):
+    """Several datasets [(x0, y0), (x1, y1), ...] as one block: x (rows, num_params) and y (rows,) stacked in order,
+    and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1])."""
+    try:
+        pairs = [_data_arrays(d, num_params) for d in datasets]
+    except TypeError:
+        raise ValueError("datasets must be a sequence of (x, y) pairs") from None
+    if not pairs:
+        raise ValueError("datasets needs at least one (x, y) pair")
+    offsets = np.zeros(len(pairs) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([y.size for _, y in pairs])
+    x = np.ascontiguousarray(np.concatenate([x for x, _ in pairs], axis=0))
+    y = np.ascontiguousarray(np.concatenate([y for _, y in pairs]))
+    return x, y, offsets
+
+
 class DeviceEngine:
     def __init__(self, model: int, dim: int, num_chains: int, cfg: Optional[_ffi.Config] = None,
-                 params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None):
+                 params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None, datasets=None):
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
-        (num_obs, dim) and y of shape (num_obs,); copied to the device once."""
+        (num_obs, dim) and y of shape (num_obs,); copied to the device once.
+
+        `datasets=[(x0, y0), (x1, y1), ...]` instead: G datasets of the same model and prior (sizes may differ), fitted
+        side by side (wn_engine_create_with_datasets).  num_chains must be a multiple k of G; chains [g*k, (g+1)*k)
+        are conditioned on dataset g and evolve exactly as chains 0..k-1 of an engine built with data=(xg, yg) and
+        seeded with chain_offset = g*k.  Per-dataset statistics: rhat_per_dataset(), warmup_spread_per_dataset();
+        init_masses_from_grad(average=True) averages over each dataset's chains."""
+        if data is not None and datasets is not None:
+            raise ValueError("data and datasets are mutually exclusive")
         self.lib = _ffi.load_library(lib_path)
         self.cfg = cfg if cfg is not None else default_config(lib_path)
         self.C, self.D = int(num_chains), int(dim)
@@ -76,7 +100,13 @@ class DeviceEngine:
             raise ValueError("model params must have num_params entries")
         h, err = C.c_void_p(), C.c_void_p()
         pp = None if p is None else p.ctypes.data_as(_dp)
-        if data is None:
+        self._several = datasets is not None
+        if datasets is not None:
+            x, y, off = _datasets_arrays(datasets, self.D)
+            rc = self.lib.wn_engine_create_with_datasets(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
+                                                         y.ctypes.data_as(_dp), off.ctypes.data_as(_ffi._i64p),
+                                                         off.size - 1, num_chains, C.byref(self.cfg), C.byref(err))
+        elif data is None:
             rc = self.lib.wn_engine_create(C.byref(h), model, dim, pp, num_chains, C.byref(self.cfg), C.byref(err))
         else:
             x, y = _data_arrays(data, self.D)
@@ -121,7 +151,12 @@ class DeviceEngine:
         """InitConfigBuilder::masses(logp_grad, smoothing, average_masses) (config.hpp:360-382)."""
         self._call(self.lib.wn_engine_init_masses_from_grad, smoothing)
         if average:
-            self._call(self.lib.wn_engine_average_masses)
+            self.average_masses()
+
+    def average_masses(self):
+        """Every chain's masses become their geometric mean over the chains (config.hpp:371-380) -- over the chains of
+        its own dataset on an engine built with `datasets=` (wn_engine_average_masses_datasets)."""
+        self._call(self.lib.wn_engine_average_masses_datasets if self._several else self.lib.wn_engine_average_masses)
 
     def adapt_step(self, seed: int, chain_offset: int = 0):
         self._call(self.lib.wn_engine_adapt_step, seed, chain_offset)
@@ -261,6 +296,22 @@ class DeviceEngine:
         a, b = C.c_double(), C.c_double()
         self._call(self.lib.wn_engine_warmup_spread, C.cast(C.byref(a), _dp), C.cast(C.byref(b), _dp))
         return a.value, b.value
+
+    @property
+    def num_datasets(self) -> int:
+        """Datasets the engine holds (1 unless built with `datasets=`)."""
+        return int(self.lib.wn_engine_num_datasets(self.h))
+
+    def rhat_per_dataset(self) -> np.ndarray:
+        """[G] R-hat of the log density per dataset: entry g is what rhat() returns on a standalone engine of dataset
+        g's chains (wn_engine_rhat_datasets)."""
+        return self._get(self.lib.wn_engine_rhat_datasets, (self.num_datasets,))
+
+    def warmup_spread_per_dataset(self):
+        """(step [G], mass [G]): warmup_spread() of each dataset's chains (wn_engine_warmup_spread_datasets)."""
+        step, mass = np.empty(self.num_datasets), np.empty(self.num_datasets)
+        self._call(self.lib.wn_engine_warmup_spread_datasets, step.ctypes.data_as(_dp), mass.ctypes.data_as(_dp))
+        return step, mass
 
     def warmup_sums(self):
         """Stage 1 of the warmup statistic for a multi-GPU driver: (sum over this engine's chains of log step,

@@ -65,6 +65,30 @@ class MarkovChains:
         _ffi.check(lib, rc, err)
         return cls(h, lib)
 
+    def chain_blocks(self, num_blocks: int, max_len: int, lengths: Sequence[int]):
+        """Views of `num_blocks` equal contiguous blocks of these chains (chains [b*k, (b+1)*k), k = num_chains /
+        num_blocks), e.g. one per dataset of walnuts_device(datasets=..., keep_on_device=True).  The chains must be a
+        [C][max_len][D] block on the device (as the sampler leaves them); `lengths` [C] are the chains' draw counts.
+        Each view keeps this handle -- and so the draws -- alive while it exists."""
+        n = self.num_chains()
+        if num_blocks < 1 or n % num_blocks:
+            raise ValueError("num_chains must be a multiple of num_blocks")
+        k, D = n // num_blocks, self.dims()
+        base = self.lib.wn_chains_device_draws(self._h)
+        device = int(self.lib.wn_chains_device(self._h))
+        lengths = np.asarray(lengths, dtype=np.int64)
+        views = []
+        for b in range(num_blocks):
+            ln = np.ascontiguousarray(lengths[b * k:(b + 1) * k])
+            h, err = C.c_void_p(), C.c_void_p()
+            rc = self.lib.wn_chains_view(C.byref(h), C.c_void_p(base + b * k * max_len * D * 8), k, max_len, D,
+                                         max_len * D, ln.ctypes.data_as(_ip), device, None, C.byref(err))
+            _ffi.check(self.lib, rc, err)
+            v = MarkovChains(h, self.lib)
+            v._owner = self
+            views.append(v)
+        return views
+
     # MarkovChainSequence accessors (concepts.hpp / summary.hpp:160-240)
     def num_chains(self) -> int:
         return int(self.lib.wn_chains_num_chains(self._h))
