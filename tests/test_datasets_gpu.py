@@ -2,6 +2,8 @@
 
   * device = emulation, bit for bit, for batched engines at (1, 2), (1, 4) and (1, 16), both arithmetic modes;
   * (1, 8), which the emulation does not build: batched = standalone engines on the device, bit for bit;
+  * the per-dataset statistics = standalone device engines' pooled ones, bit for bit, at 300 chains per dataset (each
+    dataset's 256-chain runs start at its own offset);
   * an observation block over 4 GiB after padding (a 32-bit byte offset would wrap): gradients of the last datasets'
     chains against the high-precision reference, and a short run that is finite and deterministic;
   * linear regression on datasets with distinct coefficients through walnuts_device(datasets=..., keep_on_device=True):
@@ -20,7 +22,8 @@ import build as simbuild  # noqa: E402
 import hp_reference as hp  # noqa: E402
 import walnuts_amd as wa  # noqa: E402
 from test_data_models_sim import LIN, LOG  # noqa: E402
-from test_datasets_sim import DIM, compare_blocks, config, dataset_sizes, drive, make_datasets  # noqa: E402
+from test_datasets_sim import (DIM, check_statistics_per_dataset, compare_blocks, config, dataset_sizes, drive,  # noqa: E402
+                               make_datasets)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +63,11 @@ def test_eight_per_lane_equals_standalone_engines(gpu, model, fma):
         compare_blocks(batched, drive(alone, g * k), g, k)
         alone.close()
     e.close()
+
+
+@pytest.mark.timeout(1800)
+def test_statistics_per_dataset_on_device(gpu):
+    check_statistics_per_dataset(None, 300)
 
 
 @pytest.mark.timeout(3600)

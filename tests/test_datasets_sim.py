@@ -4,6 +4,7 @@ walnutpie_sample_device_datasets*, walnuts_device(datasets=...)) under the workg
 The contract checked here: chain c of dataset g = c // k evolves bit for bit as chain c - g*k of a standalone engine
 built from dataset g alone and seeded with chain_offset = g*k; the per-dataset statistics equal the standalone engines'
 pooled ones; identical datasets give the shared-data engine; the drop-in call stops per dataset in lock step."""
+import math
 import os
 import sys
 
@@ -139,7 +140,12 @@ def test_logp_grad_against_high_precision(sim, model, geometry):
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("k", [3, 7])
 def test_statistics_per_dataset(sim, k):
-    """rhat_per_dataset, warmup_spread_per_dataset and per-dataset mass averaging equal the standalone engines'."""
+    check_statistics_per_dataset(sim, k)
+
+
+def check_statistics_per_dataset(sim, k):
+    """rhat_per_dataset, warmup_spread_per_dataset and per-dataset mass averaging equal the standalone engines'; the
+    pooled statistics are their two stages composed; at G = 1 the per-dataset statistics are the pooled ones."""
     model, D = LOG, 7
     datasets, s2 = make_datasets(model, D, [5, 1, 12], seed=31)
     cfg = config(sim, (1, 2), 1)
@@ -159,6 +165,7 @@ def test_statistics_per_dataset(sim, k):
         s_ref, m_ref = a.warmup_spread()
         assert step[g] == s_ref and mass[g] == m_ref, g
     assert len(set(step.tolist())) == 3  # (the datasets' values differ: nothing is pooled)
+    assert_pooled_spread_is_its_stages(e)
     for eng, _ in engines:
         eng.freeze()
         eng.sample_steps(6)
@@ -171,6 +178,48 @@ def test_statistics_per_dataset(sim, k):
     with pytest.raises(ValueError, match="holds no datasets"):
         pooled.rhat_per_dataset()
     assert np.isfinite(e.rhat())
+    assert_pooled_rhat_is_its_stages(e)
+    check_one_dataset(sim, model, D, k, cfg, s2, datasets[1])
+
+
+def assert_pooled_spread_is_its_stages(e):
+    """warmup_spread() is warmup_sums -> warmup_max_rel over all of the engine's chains."""
+    s, col = e.warmup_sums()
+    assert e.warmup_spread() == e.warmup_max_rel(s, col, e.C)
+
+
+def assert_pooled_rhat_is_its_stages(e):
+    """rhat() is lp_sums -> lp_sq_dev(mean of means) -> sqrt(1 + variance of means / mean of variances)."""
+    s0, s1, n = e.lp_sums()
+    q = e.lp_sq_dev(s0 / n)
+    assert e.rhat() == math.sqrt(1 + (q / (n - 1)) / (s1 / n))
+
+
+def check_one_dataset(lib, model, D, k, cfg, s2, d):
+    """An engine built with datasets=[d] (G = 1): the per-dataset statistics and mass averaging are the pooled ones."""
+    pair = [wa.DeviceEngine(model, D, k, cfg, params=s2, lib_path=lib, datasets=[d]) for _ in range(2)]
+    for u, fn in zip(pair, ("wn_engine_average_masses", "wn_engine_average_masses_datasets")):
+        assert u.num_datasets == 1
+        u.init_positions(seed=4, chain_offset=0, scale=0.5)
+        u.init_masses_from_grad(1e-5)
+        u._call(getattr(u.lib, fn))
+    m = pair[0].masses()
+    assert np.array_equal(m, pair[1].masses())
+    assert np.all(m == m[0]) and not np.all(m == 1.0)
+    u = pair[0]
+    u.adapt_step(seed=5)
+    u.seed_chains(6)
+    u.warmup_steps(4)
+    step, mass = u.warmup_spread_per_dataset()
+    assert (step[0], mass[0]) == u.warmup_spread()
+    assert_pooled_spread_is_its_stages(u)
+    u.freeze()
+    u.sample_steps(6)
+    assert np.isfinite(u.rhat())
+    assert u.rhat_per_dataset()[0] == u.rhat()
+    assert_pooled_rhat_is_its_stages(u)
+    for u in pair:
+        u.close()
 
 
 DROP_IN = dict(seed=9, id=2, init_radius=0.5, max_trajectory_doublings=4)

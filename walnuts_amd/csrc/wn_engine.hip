@@ -18,6 +18,7 @@
 #include "wn_elementwise.h"
 #include "wn_init.h"
 #include "wn_launch.h"
+#include "wn_monitor.h"
 #include "wn_traj.h"
 
 #include "wn_host.h"
@@ -61,7 +62,9 @@ struct wn_engine {
 
   DevBuf<double> theta, mass, inv_mass, chol_mass, draw_mean, draw_ssd, score_mean, score_ssd;
   DevBuf<double> step_init, step_size, adam, est_weight, mm_state, logp, model_params, arena, z_buf, u_buf;
-  DevBuf<double> lp_stats, mon_partial, mon_out, mon_colsum, mon_rel_mass, mon_rel_step;
+  // the cross-chain monitors (wn_elementwise.h): run partials, stage-1 sums [G][1 + D] (R-hat: [G][2]; mass averaging:
+  // [G][D]), stage-2 results [G][2], and per chain the relative distances of the warmup spread
+  DevBuf<double> lp_stats, mon_runs, mon_sums, mon_out, mon_rel_mass, mon_rel_step;
   DevBuf<double> data_x, data_y;  // a data model's observations: [num_obs][Dp] (rows padded with zeros), [num_obs]
   int num_obs = 0;
   // several datasets (wn_engine_create_with_datasets): data_x / data_y hold them one after another, dataset g being rows
@@ -69,9 +72,6 @@ struct wn_engine {
   DevBuf<int64_t> data_offsets;
   int num_datasets = 1;
   int chains_per_dataset = 0;
-  // the per-dataset monitors' buffers (allocated with the datasets): run partials, [G][2] sums, [G] second-stage sums,
-  // [G][D] column sums, [G][2] maxima
-  DevBuf<double> ds_partial, ds_sums, ds_q, ds_colsum, ds_max;
   DevBuf<int32_t> min_micro, depth, rng_draws, failed_ext;
   DevBuf<int64_t> grad_evals;
   DevBuf<uint32_t> counter, error_flags;
@@ -610,9 +610,6 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   e.error_flags.alloc(1);
   HIP_OK(hipMemsetAsync(e.error_flags.p, 0, sizeof(uint32_t), e.stream));
   e.lp_stats.alloc(3 * num_chains);
-  e.mon_partial.alloc(2 * static_cast<size_t>(wn::monitor_runs(static_cast<int>(num_chains))));
-  e.mon_out.alloc(4);
-  e.mon_colsum.alloc(e.Dp);
   e.mon_rel_mass.alloc(num_chains);
   e.mon_rel_step.alloc(num_chains);
   e.scratch64.alloc(1);
@@ -675,13 +672,14 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     HIP_OK(hipMemcpyAsync(e.data_y.p, data->y, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
     HIP_OK(hipMemcpyAsync(e.data_offsets.p, data->offsets, (static_cast<size_t>(G) + 1) * sizeof(int64_t),
                           hipMemcpyHostToDevice, e.stream));
-    const size_t k = static_cast<size_t>(e.chains_per_dataset);
-    e.ds_partial.alloc(2 * static_cast<size_t>(G) * static_cast<size_t>(wn::monitor_runs(static_cast<int>(k))));
-    e.ds_sums.alloc(2 * static_cast<size_t>(G));
-    e.ds_q.alloc(static_cast<size_t>(G));
-    e.ds_colsum.alloc(static_cast<size_t>(G) * static_cast<size_t>(num_params));
-    e.ds_max.alloc(2 * static_cast<size_t>(G));
     HIP_OK(hipStreamSynchronize(e.stream));
+  }
+  {
+    // sized for the engine's G segments of k chains, which covers the pooled (1, C): G * runs(k) >= runs(G * k)
+    const size_t G = static_cast<size_t>(e.num_datasets);
+    e.mon_runs.alloc(2 * G * static_cast<size_t>(wn::monitor_runs(static_cast<int>(num_chains / G))));
+    e.mon_sums.alloc(G * (1 + static_cast<size_t>(e.D)));
+    e.mon_out.alloc(2 * G);
   }
   wn::prepare_kernels(model, e.geo, e.smem);
 }
@@ -989,19 +987,6 @@ int wn_engine_init_masses_from_grad(wn_engine* e, double smoothing, WalnutpyErro
     run_init(*e, false, true, false, 1.0, smoothing, 0, 0, 0, 0);
   });
 }
-int wn_engine_average_masses(wn_engine* e, WalnutpyError** err) {
-  return guarded(err, [&] {
-    e->use_device();
-    const int C = static_cast<int>(e->C);
-    hipLaunchKernelGGL(wn::mass_log_colsum_kernel, dim3((e->D + 255) / 256), dim3(256), 0, e->stream, C, e->D, e->Dp,
-                       e->mass.p, e->mon_colsum.p);
-    const int blocks = static_cast<int>(std::min<size_t>((e->C * e->Dp + 255) / 256, 4096));
-    hipLaunchKernelGGL(wn::mass_broadcast_kernel, dim3(blocks), dim3(256), 0, e->stream, C, e->D, e->Dp,
-                       e->mon_colsum.p, e->mass.p);
-    HIP_OK(hipGetLastError());
-    e->adapters_ready = false;
-  });
-}
 int wn_engine_get_masses(wn_engine* e, double* out, WalnutpyError** err) {
   return guarded(err, [&] {
     if (e == nullptr || out == nullptr) throw std::invalid_argument("null argument"); e->download_rows(e->mass, out); });
@@ -1224,63 +1209,127 @@ int wn_engine_total_grad_evals(wn_engine* e, int64_t* out, WalnutpyError** err) 
 }
 
 // ---- cross-chain monitors (adapt.hpp:172-229, sampler.hpp:117-158) ---------------------------------
+// One routine per statistic over G segments of k consecutive chains (wn_elementwise.h).  The pooled entry points run it
+// at (1, C); the _datasets ones at (num_datasets, chains_per_dataset), where dataset g's value is what the pooled entry
+// point returns on a standalone engine of its k chains.  The two stages a multi-GPU driver all-reduces in between
+// (wn_engine_lp_sums / _lp_sq_dev, wn_engine_warmup_sums / _warmup_max_rel) are the routines' stages at G = 1.
+namespace {
+int monitor_grid(size_t n) { return static_cast<int>(std::max<size_t>(1, (n + 255) / 256)); }
+
+// R-hat, stage 1 -> mon_sums[G][2]: the sums of the chains' lp means and sample variances
+void lp_sums_stage(wn_engine& e, int G, int k) {
+  const int per = wn::monitor_runs(k);
+  hipLaunchKernelGGL(wn::lp_sums_kernel, dim3(monitor_grid(static_cast<size_t>(G) * per)), dim3(256), 0, e.stream, G, k,
+                     e.lp_stats.p, e.mon_runs.p);
+  hipLaunchKernelGGL(wn::finish_sums_kernel<2>, dim3(monitor_grid(G)), dim3(256), 0, e.stream, e.mon_runs.p, G, per,
+                     e.mon_sums.p, 2);
+  HIP_OK(hipGetLastError());
+}
+// stage 2 -> mon_out[G]: the sums of squared deviations from the means of means mon_sums[2g] / n
+void lp_sq_dev_stage(wn_engine& e, int G, int k, double n) {
+  const int per = wn::monitor_runs(k);
+  hipLaunchKernelGGL(wn::lp_sqdev_kernel, dim3(monitor_grid(static_cast<size_t>(G) * per)), dim3(256), 0, e.stream, G,
+                     k, e.lp_stats.p, e.mon_sums.p, n, e.mon_runs.p);
+  hipLaunchKernelGGL(wn::finish_sums_kernel<1>, dim3(monitor_grid(G)), dim3(256), 0, e.stream, e.mon_runs.p, G, per,
+                     e.mon_out.p, 1);
+  HIP_OK(hipGetLastError());
+}
+void rhat_segments(wn_engine& e, int G, int k, double* rhat) {
+  e.use_device();
+  lp_sums_stage(e, G, k);
+  lp_sq_dev_stage(e, G, k, k);
+  std::vector<double> s(2 * static_cast<size_t>(G)), q(static_cast<size_t>(G));
+  e.download(e.mon_sums, s.data(), s.size());
+  e.download(e.mon_out, q.data(), q.size());
+  for (int g = 0; g < G; ++g) rhat[g] = wn::rhat_from_sums(s[2 * g + 1], q[g], k);
+}
+
+void begin_warmup_monitor(wn_engine& e) {
+  if (e.frozen) throw std::runtime_error("warmup monitor after freeze");
+  e.ensure_adapters();
+  e.use_device();
+}
+// warmup spread, stage 1 -> mon_sums[G][1 + D]: the sums of log step, then of log mass per dimension
+void warmup_sums_stage(wn_engine& e, int G, int k) {
+  const int per = wn::monitor_runs(k);
+  hipLaunchKernelGGL(wn::log_step_sum_kernel, dim3(monitor_grid(static_cast<size_t>(G) * per)), dim3(256), 0, e.stream,
+                     G, k, e.adam.p, e.mon_runs.p);
+  hipLaunchKernelGGL(wn::finish_sums_kernel<1>, dim3(monitor_grid(G)), dim3(256), 0, e.stream, e.mon_runs.p, G, per,
+                     e.mon_sums.p, 1 + e.D);
+  hipLaunchKernelGGL(wn::log_mass_colsum_kernel, dim3(monitor_grid(static_cast<size_t>(G) * e.D)), dim3(256), 0,
+                     e.stream, G, k, e.D, e.Dp, e.draw_ssd.p, e.score_ssd.p, e.est_weight.p, e.mon_sums.p);
+  HIP_OK(hipGetLastError());
+}
+// stage 2 -> mon_out[G][2]: the largest relative distances (mass, step) from the geometric means of mon_sums over n
+// chains
+void warmup_max_rel_stage(wn_engine& e, int G, int k, double n) {
+  hipLaunchKernelGGL(wn::warmup_spread_kernel, dim3(G * k), dim3(256), 0, e.stream, k, e.D, e.Dp, e.draw_ssd.p,
+                     e.score_ssd.p, e.est_weight.p, e.adam.p, e.mon_sums.p, n, e.mon_rel_mass.p, e.mon_rel_step.p);
+  hipLaunchKernelGGL(wn::max2_kernel, dim3(G), dim3(256), 0, e.stream, k, e.mon_rel_mass.p, e.mon_rel_step.p,
+                     e.mon_out.p);
+  HIP_OK(hipGetLastError());
+}
+void warmup_spread_segments(wn_engine& e, int G, int k, double* max_rel_diff_step, double* max_rel_diff_mass) {
+  begin_warmup_monitor(e);
+  warmup_sums_stage(e, G, k);
+  warmup_max_rel_stage(e, G, k, k);
+  std::vector<double> m(2 * static_cast<size_t>(G));
+  e.download(e.mon_out, m.data(), m.size());
+  for (int g = 0; g < G; ++g) {
+    max_rel_diff_mass[g] = m[2 * g];
+    max_rel_diff_step[g] = m[2 * g + 1];
+  }
+}
+
+void average_masses_segments(wn_engine& e, int G, int k) {
+  e.use_device();
+  hipLaunchKernelGGL(wn::mass_log_colsum_kernel, dim3(monitor_grid(static_cast<size_t>(G) * e.D)), dim3(256), 0,
+                     e.stream, G, k, e.D, e.Dp, e.mass.p, e.mon_sums.p);
+  const int blocks = static_cast<int>(std::min<size_t>((e.C * e.Dp + 255) / 256, 4096));
+  hipLaunchKernelGGL(wn::mass_broadcast_kernel, dim3(blocks), dim3(256), 0, e.stream, static_cast<int>(e.C), k, e.D,
+                     e.Dp, e.mon_sums.p, e.mass.p);
+  HIP_OK(hipGetLastError());
+  e.adapters_ready = false;
+}
+
+void require_datasets(const wn_engine* e) {
+  if (e->chains_per_dataset == 0)
+    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_with_datasets)");
+}
+}  // namespace
+
 int wn_engine_lp_sums(wn_engine* e, double* out /*[3]: sum of means, sum of sample variances, chains*/,
                       WalnutpyError** err) {
   return guarded(err, [&] {
     e->use_device();
-    const int C = static_cast<int>(e->C);
-    const int runs = wn::monitor_runs(C);
-    hipLaunchKernelGGL(wn::lp_sums_kernel, dim3((runs + 63) / 64), dim3(64), 0, e->stream, C, e->lp_stats.p,
-                       e->mon_partial.p);
-    hipLaunchKernelGGL(wn::finish_sums_kernel<2>, dim3(1), dim3(64), 0, e->stream, e->mon_partial.p, runs, e->mon_out.p);
-    HIP_OK(hipGetLastError());
-    e->download(e->mon_out, out, 2);
-    out[2] = static_cast<double>(C);
+    lp_sums_stage(*e, 1, static_cast<int>(e->C));
+    e->download(e->mon_sums, out, 2);
+    out[2] = static_cast<double>(e->C);
   });
 }
 int wn_engine_lp_sq_dev(wn_engine* e, double mean_of_means, double* out, WalnutpyError** err) {
   return guarded(err, [&] {
     e->use_device();
-    const int runs = wn::monitor_runs(static_cast<int>(e->C));
-    hipLaunchKernelGGL(wn::lp_sqdev_kernel, dim3((runs + 63) / 64), dim3(64), 0, e->stream,
-                       static_cast<int>(e->C), e->lp_stats.p, mean_of_means, e->mon_partial.p);
-    hipLaunchKernelGGL(wn::finish_sums_kernel<1>, dim3(1), dim3(64), 0, e->stream, e->mon_partial.p, runs, e->mon_out.p);
-    HIP_OK(hipGetLastError());
+    // the caller's mean of means (over its chains on every engine) stands as the sum over one chain: x / 1 is x
+    HIP_OK(hipMemcpyAsync(e->mon_sums.p, &mean_of_means, sizeof(double), hipMemcpyHostToDevice, e->stream));
+    lp_sq_dev_stage(*e, 1, static_cast<int>(e->C), 1.0);
     e->download(e->mon_out, out, 1);
   });
 }
 int wn_engine_rhat(wn_engine* e, double* rhat, WalnutpyError** err) {
-  return guarded(err, [&] {
-    double s[3], q;
-    WalnutpyError* inner = nullptr;
-    if (wn_engine_lp_sums(e, s, &inner) != 0 || wn_engine_lp_sq_dev(e, s[0] / s[2], &q, &inner) != 0) {
-      std::string msg = inner ? inner->msg : "monitor failed";
-      delete inner;
-      throw std::runtime_error(msg);
-    }
-    const double variance_of_means = q / (s[2] - 1);  // util.hpp:401-404
-    const double mean_of_variances = s[1] / s[2];
-    *rhat = std::sqrt(1 + variance_of_means / mean_of_variances);  // sampler.hpp:145
-  });
+  return guarded(err, [&] { rhat_segments(*e, 1, static_cast<int>(e->C), rhat); });
 }
 // The warmup controller's statistic (adapt.hpp:193-221) in the two stages a multi-GPU driver needs: (1) this
 // engine's sums over chains of log step and of log mass per dimension -- D+1 doubles to all-reduce (SUM) --,
 // (2) given the sums over ALL chains, this engine's largest relative distances -- 2 doubles to all-reduce (MAX).
 int wn_engine_warmup_sums(wn_engine* e, double* sum_log_step, double* colsum_log_mass, WalnutpyError** err) {
   return guarded(err, [&] {
-    if (e->frozen) throw std::runtime_error("warmup monitor after freeze");
-    e->ensure_adapters();
-    e->use_device();
-    const int C = static_cast<int>(e->C);
-    const int runs = wn::monitor_runs(C);
-    hipLaunchKernelGGL(wn::log_step_sum_kernel, dim3((runs + 63) / 64), dim3(64), 0, e->stream, C, e->adam.p,
-                       e->mon_partial.p);
-    hipLaunchKernelGGL(wn::finish_sums_kernel<1>, dim3(1), dim3(64), 0, e->stream, e->mon_partial.p, runs, e->mon_out.p);
-    hipLaunchKernelGGL(wn::log_mass_colsum_kernel, dim3((e->D + 255) / 256), dim3(256), 0, e->stream, C, e->D, e->Dp,
-                       e->draw_ssd.p, e->score_ssd.p, e->est_weight.p, e->mon_colsum.p);
-    HIP_OK(hipGetLastError());
-    e->download(e->mon_out, sum_log_step, 1);
-    e->download(e->mon_colsum, colsum_log_mass, static_cast<size_t>(e->D));
+    begin_warmup_monitor(*e);
+    warmup_sums_stage(*e, 1, static_cast<int>(e->C));
+    std::vector<double> sums(1 + static_cast<size_t>(e->D));
+    e->download(e->mon_sums, sums.data(), sums.size());
+    *sum_log_step = sums[0];
+    std::copy(sums.begin() + 1, sums.end(), colsum_log_mass);
   });
 }
 int wn_engine_warmup_max_rel(wn_engine* e, double sum_log_step, const double* colsum_log_mass, size_t total_chains,
@@ -1290,17 +1339,11 @@ int wn_engine_warmup_max_rel(wn_engine* e, double sum_log_step, const double* co
     if (total_chains < e->C) throw std::invalid_argument("total_chains is smaller than this engine's chain count");
     e->ensure_adapters();
     e->use_device();
-    const int C = static_cast<int>(e->C);
-    HIP_OK(hipMemcpyAsync(e->mon_colsum.p, colsum_log_mass, static_cast<size_t>(e->D) * sizeof(double),
-                          hipMemcpyHostToDevice, e->stream));
-    const double n = static_cast<double>(total_chains);
-    const double mean_log_step = sum_log_step / n;  // adapt.hpp:201-202
-    hipLaunchKernelGGL(wn::warmup_spread_kernel, dim3(C), dim3(256), 0, e->stream, C, e->D, e->Dp, e->draw_ssd.p,
-                       e->score_ssd.p, e->est_weight.p, e->adam.p, e->mon_colsum.p, n, mean_log_step,
-                       e->mon_rel_mass.p, e->mon_rel_step.p);
-    hipLaunchKernelGGL(wn::max2_kernel, dim3(1), dim3(256), 0, e->stream, C, e->mon_rel_mass.p, e->mon_rel_step.p,
-                       e->mon_out.p);
-    HIP_OK(hipGetLastError());
+    std::vector<double> sums(1 + static_cast<size_t>(e->D));
+    sums[0] = sum_log_step;
+    std::copy(colsum_log_mass, colsum_log_mass + e->D, sums.begin() + 1);
+    HIP_OK(hipMemcpyAsync(e->mon_sums.p, sums.data(), sums.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    warmup_max_rel_stage(*e, 1, static_cast<int>(e->C), static_cast<double>(total_chains));
     double m[2];
     e->download(e->mon_out, m, 2);
     *max_rel_diff_mass = m[0];
@@ -1309,56 +1352,18 @@ int wn_engine_warmup_max_rel(wn_engine* e, double sum_log_step, const double* co
 }
 int wn_engine_warmup_spread(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass, WalnutpyError** err) {
   return guarded(err, [&] {
-    WalnutpyError* inner = nullptr;
-    double sum_log_step = 0;
-    std::vector<double> colsum(static_cast<size_t>(e->D));
-    if (wn_engine_warmup_sums(e, &sum_log_step, colsum.data(), &inner) != 0 ||
-        wn_engine_warmup_max_rel(e, sum_log_step, colsum.data(), e->C, max_rel_diff_step, max_rel_diff_mass, &inner) != 0) {
-      const std::string msg = inner ? inner->msg : "monitor failed";
-      delete inner;
-      throw std::runtime_error(msg);
-    }
+    warmup_spread_segments(*e, 1, static_cast<int>(e->C), max_rel_diff_step, max_rel_diff_mass);
   });
 }
-
-// ---- the same monitors per dataset (wn_engine_create_with_datasets) ---------------------------------------------------
-// Dataset g's value is, bit for bit, what wn_engine_rhat / wn_engine_warmup_spread / wn_engine_average_masses return on a
-// standalone engine of its k chains: the kernels of wn_elementwise.h (*_ds_kernel) keep the pooled kernels' order within
-// each dataset, and each stage is one launch whatever the number of datasets.  On an engine with one shared data block
-// (or none) the one "dataset" is all chains.
-namespace {
-void require_datasets(const wn_engine* e) {
-  if (e->chains_per_dataset == 0)
-    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_with_datasets)");
+int wn_engine_average_masses(wn_engine* e, WalnutpyError** err) {
+  return guarded(err, [&] { average_masses_segments(*e, 1, static_cast<int>(e->C)); });
 }
-int ds_grid(size_t n) { return static_cast<int>(std::max<size_t>(1, (n + 255) / 256)); }
-}  // namespace
 
 int wn_engine_rhat_datasets(wn_engine* e, double* rhat, WalnutpyError** err) {
   return guarded(err, [&] {
     if (rhat == nullptr) throw std::invalid_argument("null argument");
     require_datasets(e);
-    e->use_device();
-    const int G = e->num_datasets, k = e->chains_per_dataset, per = wn::monitor_runs(k);
-    const size_t runs = static_cast<size_t>(G) * per;
-    hipLaunchKernelGGL(wn::lp_sums_ds_kernel, dim3(ds_grid(runs)), dim3(256), 0, e->stream, G, k, e->lp_stats.p,
-                       e->ds_partial.p);
-    hipLaunchKernelGGL(wn::finish_sums_ds_kernel<2>, dim3(ds_grid(G)), dim3(256), 0, e->stream, e->ds_partial.p, G, per,
-                       e->ds_sums.p);
-    hipLaunchKernelGGL(wn::lp_sqdev_ds_kernel, dim3(ds_grid(runs)), dim3(256), 0, e->stream, G, k, e->lp_stats.p,
-                       e->ds_sums.p, e->ds_partial.p);
-    hipLaunchKernelGGL(wn::finish_sums_ds_kernel<1>, dim3(ds_grid(G)), dim3(256), 0, e->stream, e->ds_partial.p, G, per,
-                       e->ds_q.p);
-    HIP_OK(hipGetLastError());
-    std::vector<double> s(2 * static_cast<size_t>(G)), q(static_cast<size_t>(G));
-    e->download(e->ds_sums, s.data(), s.size());
-    e->download(e->ds_q, q.data(), q.size());
-    const double n = static_cast<double>(k);
-    for (int g = 0; g < G; ++g) {  // wn_engine_rhat's arithmetic
-      const double variance_of_means = q[g] / (n - 1);
-      const double mean_of_variances = s[2 * g + 1] / n;
-      rhat[g] = std::sqrt(1 + variance_of_means / mean_of_variances);
-    }
+    rhat_segments(*e, e->num_datasets, e->chains_per_dataset, rhat);
   });
 }
 int wn_engine_warmup_spread_datasets(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
@@ -1366,43 +1371,24 @@ int wn_engine_warmup_spread_datasets(wn_engine* e, double* max_rel_diff_step, do
   return guarded(err, [&] {
     if (max_rel_diff_step == nullptr || max_rel_diff_mass == nullptr) throw std::invalid_argument("null argument");
     require_datasets(e);
-    if (e->frozen) throw std::runtime_error("warmup monitor after freeze");
-    e->ensure_adapters();
-    e->use_device();
-    const int G = e->num_datasets, k = e->chains_per_dataset, per = wn::monitor_runs(k), C = static_cast<int>(e->C);
-    const size_t runs = static_cast<size_t>(G) * per;
-    hipLaunchKernelGGL(wn::log_step_sum_ds_kernel, dim3(ds_grid(runs)), dim3(256), 0, e->stream, G, k, e->adam.p,
-                       e->ds_partial.p);
-    hipLaunchKernelGGL(wn::finish_sums_ds_kernel<1>, dim3(ds_grid(G)), dim3(256), 0, e->stream, e->ds_partial.p, G, per,
-                       e->ds_q.p);
-    hipLaunchKernelGGL(wn::log_mass_colsum_ds_kernel, dim3(ds_grid(static_cast<size_t>(G) * e->D)), dim3(256), 0,
-                       e->stream, G, k, e->D, e->Dp, e->draw_ssd.p, e->score_ssd.p, e->est_weight.p, e->ds_colsum.p);
-    hipLaunchKernelGGL(wn::warmup_spread_ds_kernel, dim3(C), dim3(256), 0, e->stream, k, e->D, e->Dp, e->draw_ssd.p,
-                       e->score_ssd.p, e->est_weight.p, e->adam.p, e->ds_colsum.p, e->ds_q.p, e->mon_rel_mass.p,
-                       e->mon_rel_step.p);
-    hipLaunchKernelGGL(wn::max2_ds_kernel, dim3(G), dim3(256), 0, e->stream, k, e->mon_rel_mass.p, e->mon_rel_step.p,
-                       e->ds_max.p);
-    HIP_OK(hipGetLastError());
-    std::vector<double> m(2 * static_cast<size_t>(G));
-    e->download(e->ds_max, m.data(), m.size());
-    for (int g = 0; g < G; ++g) {
-      max_rel_diff_mass[g] = m[2 * g];
-      max_rel_diff_step[g] = m[2 * g + 1];
-    }
+    warmup_spread_segments(*e, e->num_datasets, e->chains_per_dataset, max_rel_diff_step, max_rel_diff_mass);
   });
 }
 int wn_engine_average_masses_datasets(wn_engine* e, WalnutpyError** err) {
   return guarded(err, [&] {
     require_datasets(e);
-    e->use_device();
-    const int G = e->num_datasets, k = e->chains_per_dataset, C = static_cast<int>(e->C);
-    hipLaunchKernelGGL(wn::mass_log_colsum_ds_kernel, dim3(ds_grid(static_cast<size_t>(G) * e->D)), dim3(256), 0,
-                       e->stream, G, k, e->D, e->Dp, e->mass.p, e->ds_colsum.p);
-    const int blocks = static_cast<int>(std::min<size_t>((e->C * e->Dp + 255) / 256, 4096));
-    hipLaunchKernelGGL(wn::mass_broadcast_ds_kernel, dim3(blocks), dim3(256), 0, e->stream, C, k, e->D, e->Dp,
-                       e->ds_colsum.p, e->mass.p);
-    HIP_OK(hipGetLastError());
-    e->adapters_ready = false;
+    average_masses_segments(*e, e->num_datasets, e->chains_per_dataset);
+  });
+}
+// The driver's one-shard controller looks (wn_sample.hip): per dataset, or pooled on an engine without datasets
+extern "C" int wn_internal_rhat_segments(wn_engine* e, double* rhat, WalnutpyError** err) {
+  return guarded(err, [&] { rhat_segments(*e, e->num_datasets, static_cast<int>(e->C) / e->num_datasets, rhat); });
+}
+extern "C" int wn_internal_warmup_spread_segments(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
+                                                  WalnutpyError** err) {
+  return guarded(err, [&] {
+    warmup_spread_segments(*e, e->num_datasets, static_cast<int>(e->C) / e->num_datasets, max_rel_diff_step,
+                           max_rel_diff_mass);
   });
 }
 

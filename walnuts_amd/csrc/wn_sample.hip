@@ -44,10 +44,15 @@
 #include <unistd.h>
 
 #include "../../include/walnuts_hip.h"
+#include "wn_monitor.h"
 #include "wn_refstream.h"
 
 extern "C" int wn_engine_adapt_step_with_normals(wn_engine* e, const double* normals, WalnutpyError** err);
 extern "C" void* wn_internal_make_error(const char* msg, int type);
+// the controllers' look at one engine, per dataset (wn_engine_*_datasets) or pooled on an engine without datasets
+extern "C" int wn_internal_rhat_segments(wn_engine* e, double* rhat, WalnutpyError** err);
+extern "C" int wn_internal_warmup_spread_segments(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
+                                                  WalnutpyError** err);
 
 namespace {
 
@@ -680,19 +685,15 @@ namespace {
 // The chains shard embarrassingly (adapt.hpp:257-258: nothing is pooled per transition): shard s is a contiguous block
 // of GLOBAL chain ids on devices[s], driven by its own host thread, engine and stream, and writes its own slice of the
 // caller's out[C][T][D] -- no exchange on the data path.  What the shards share is what the reference's controller
-// threads look at: the warmup spread (adapt.hpp:193-221) and R-hat of the log density (sampler.hpp:139-145), each
-// reduced in the two stages the engine exposes (wn_engine_warmup_sums / _warmup_max_rel, wn_engine_lp_sums / _lp_sq_dev)
-// with a rendezvous of the shard threads in between, so that every shard takes the same stopping decision at the same
-// iteration.  A one-device call is the one-shard case: every reduction starts from shard 0's value, so one shard
-// reproduces wn_engine_warmup_spread and wn_engine_rhat bit for bit.
+// threads look at: the warmup spread (adapt.hpp:193-221) and R-hat of the log density (sampler.hpp:139-145).  Several
+// shards reduce each in the two stages the engine exposes (wn_engine_warmup_sums / _warmup_max_rel, wn_engine_lp_sums
+// / _lp_sq_dev) with a rendezvous of the shard threads in between, so that every shard takes the same stopping decision
+// at the same iteration.  One shard takes the statistic of each of its engine's datasets (the pooled one without
+// datasets) in one call, and the call stops when every dataset meets the rule.
 struct ShardAborted {};  // another shard failed: leave quietly, the wrapper reports that shard's error
 class Coordinator {
  public:
-  // datasets > 0: one shard whose engine holds that many datasets (wn_engine_create_with_datasets); each statistic is
-  // then taken per dataset and every dataset has to meet the rule
-  Coordinator(int shards, size_t dims, int datasets = 0)
-      : n_(shards), D_(dims), G_(datasets), slots_(static_cast<size_t>(shards) * (dims + 4), 0.0) {}
-  int datasets() const { return G_ > 0 ? G_ : 1; }
+  Coordinator(int shards, size_t dims) : n_(shards), D_(dims), slots_(static_cast<size_t>(shards) * (dims + 4), 0.0) {}
   // a failing shard stops taking part; the others notice at their next rendezvous
   void abandon() {
     std::lock_guard<std::mutex> lk(mu_);
@@ -701,44 +702,46 @@ class Coordinator {
     if (arrived_ >= n_ && n_ > 0) release();
     cv_.notify_all();
   }
-  // adapt.hpp:193-221 over ALL shards' chains
+  // adapt.hpp:193-221 over ALL shards' chains: every dataset's spread meets both tolerances
   bool warmup_converged(int shard, wn_engine* e, size_t total_chains, double step_tol, double mass_tol) {
-    if (G_ > 0) {  // every dataset's spread (wn_engine_warmup_spread over its chains) meets both tolerances
-      std::vector<double> step(static_cast<size_t>(G_)), mass(static_cast<size_t>(G_));
-      WN_CALL(wn_engine_warmup_spread_datasets(e, step.data(), mass.data(), &call_err_));
-      for (int g = 0; g < G_; ++g)
-        if (!(mass[g] <= mass_tol && step[g] <= step_tol)) return false;
-      return true;
+    const size_t G = static_cast<size_t>(wn_engine_num_datasets(e));
+    std::vector<double> step(G), mass(G);  // largest relative distances
+    if (total_shards_ == 1) {
+      WN_CALL(wn_internal_warmup_spread_segments(e, step.data(), mass.data(), &call_err_));
+    } else {
+      std::vector<double> sums(D_ + 1);  // sum of log step sizes, column sums of log masses
+      WN_CALL(wn_engine_warmup_sums(e, sums.data(), sums.data() + 1, &call_err_));
+      all_reduce(shard, sums.data(), D_ + 1, [](double x, double y) { return x + y; });
+      double rel[2];
+      WN_CALL(wn_engine_warmup_max_rel(e, sums[0], sums.data() + 1, total_chains, &rel[0], &rel[1], &call_err_));
+      all_reduce(shard, rel, 2, [](double x, double y) { return std::max(x, y); });
+      step[0] = rel[0];
+      mass[0] = rel[1];
     }
-    std::vector<double> sums(D_ + 1);  // sum of log step sizes, column sums of log masses
-    WN_CALL(wn_engine_warmup_sums(e, sums.data(), sums.data() + 1, &call_err_));
-    all_reduce(shard, sums.data(), D_ + 1, [](double x, double y) { return x + y; });
-    double rel[2];  // largest relative distances: step, mass
-    WN_CALL(wn_engine_warmup_max_rel(e, sums[0], sums.data() + 1, total_chains, &rel[0], &rel[1], &call_err_));
-    all_reduce(shard, rel, 2, [](double x, double y) { return std::max(x, y); });
-    return rel[1] <= mass_tol && rel[0] <= step_tol;
+    for (size_t g = 0; g < G; ++g)
+      if (!(mass[g] <= mass_tol && step[g] <= step_tol)) return false;
+    return true;
   }
-  // sampler.hpp:139-145 over ALL shards' chains
-  // (several datasets: the largest of their R-hats, NaN if any is -- at most the tolerance exactly when every one is)
+  // sampler.hpp:139-145 over ALL shards' chains: the largest of the datasets' R-hats, NaN if any is (at most the
+  // tolerance exactly when every one is)
   double rhat(int shard, wn_engine* e) {
-    if (G_ > 0) {
-      std::vector<double> r(static_cast<size_t>(G_));
-      WN_CALL(wn_engine_rhat_datasets(e, r.data(), &call_err_));
-      double m = r[0];
-      for (int g = 1; g < G_ && !std::isnan(m); ++g)
-        if (!(r[g] <= m)) m = r[g];
-      return m;
+    std::vector<double> r(static_cast<size_t>(wn_engine_num_datasets(e)));
+    if (total_shards_ == 1) {
+      WN_CALL(wn_internal_rhat_segments(e, r.data(), &call_err_));
+    } else {
+      const auto sum = [](double x, double y) { return x + y; };
+      double s[3];  // sum of means, sum of sample variances, chains
+      WN_CALL(wn_engine_lp_sums(e, s, &call_err_));
+      all_reduce(shard, s, 3, sum);
+      double q = 0;
+      WN_CALL(wn_engine_lp_sq_dev(e, s[0] / s[2], &q, &call_err_));
+      all_reduce(shard, &q, 1, sum);
+      r[0] = wn::rhat_from_sums(s[1], q, s[2]);
     }
-    const auto sum = [](double x, double y) { return x + y; };
-    double s[3];  // sum of means, sum of sample variances, chains
-    WN_CALL(wn_engine_lp_sums(e, s, &call_err_));
-    all_reduce(shard, s, 3, sum);
-    double q = 0;
-    WN_CALL(wn_engine_lp_sq_dev(e, s[0] / s[2], &q, &call_err_));
-    all_reduce(shard, &q, 1, sum);
-    const double variance_of_means = q / (s[2] - 1);  // util.hpp:401-404
-    const double mean_of_variances = s[1] / s[2];
-    return std::sqrt(1 + variance_of_means / mean_of_variances);  // sampler.hpp:145
+    double m = r[0];
+    for (size_t g = 1; g < r.size() && !std::isnan(m); ++g)
+      if (!(r[g] <= m)) m = r[g];
+    return m;
   }
 
  private:
@@ -772,7 +775,6 @@ class Coordinator {
   int n_;
   const int total_shards_ = n_;
   size_t D_;
-  int G_;
   std::vector<double> slots_;
   std::mutex mu_;
   std::condition_variable cv_;
@@ -1092,7 +1094,8 @@ struct Iterations {
     }
   }
   bool controller_looks_after(int it) const {
-    return it >= a.min_sampling_iter && it >= 2 && it < a.max_sampling_iter && shard.total_chains / coord.datasets() > 1 &&
+    const size_t chains_per_dataset = shard.total_chains / static_cast<size_t>(wn_engine_num_datasets(e));
+    return it >= a.min_sampling_iter && it >= 2 && it < a.max_sampling_iter && chains_per_dataset > 1 &&
            (it - a.min_sampling_iter) % rhat_stride == 0;
   }
   static constexpr int rhat_stride = 5;
@@ -1205,8 +1208,7 @@ void run_shard(const Model& m, const SampleArgs& a, const Mode& mode, const Plan
 int sample_one(const Model& m, const SampleArgs& a, const Mode& mode, WalnutpyError** err) {
   try {
     const Plan plan = validate(m, a, mode);
-    Coordinator one(1, static_cast<size_t>(m.num_params),
-                    mode.data != nullptr && mode.data->several ? mode.data->num_datasets : 0);
+    Coordinator one(1, static_cast<size_t>(m.num_params));
     run_shard(m, a, mode, plan, Shard{0, 0, a.num_chains, a.final_lengths, a.final_lengths + a.num_chains, nullptr}, one);
     return 0;
   } catch (...) {
