@@ -208,6 +208,59 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_datasets_resident(
     double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
     int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
     int thin, wn_chains** chains_out, WalnutpyError** err);
+/* The same four calls for a GROUPED model (kUsesGroups: hier_linear_regression, hier_logistic_regression and their
+ * _centered forms, walnuts_amd/csrc/models/hier_glm.h): group [rows] (int32, every entry in [0, num_groups)) and
+ * num_groups after y; x then has P = num_params - num_groups - 1 columns (P >= 1, num_groups >= 1).  With several
+ * datasets the groups are sliced by obs_offsets like x and y, and num_groups is shared (a dataset may leave groups
+ * empty).  Refusals as for wn_engine_create_with_grouped_data. */
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped(
+    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
+    int num_groups, int num_obs, const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    WalnutpyError** err);
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped_resident(
+    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
+    int num_groups, int num_obs, const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    int thin, wn_chains** chains_out, WalnutpyError** err);
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped_datasets(
+    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
+    int num_groups, const int64_t* obs_offsets, int num_datasets, const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    WalnutpyError** err);
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped_datasets_resident(
+    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
+    int num_groups, const int64_t* obs_offsets, int num_datasets, const double* inits, size_t num_chains,
+    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
+    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
+    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
+    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
+    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
+    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
+    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
+    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
+    int thin, wn_chains** chains_out, WalnutpyError** err);
 
 /* walnutpie_sample_device over SEVERAL devices of the node ("one process, one driver thread +
  * stream per GPU").  devices[num_devices]: HIP ordinals; shard s -- a contiguous block of the global chain ids, sizes
@@ -377,6 +430,24 @@ WALNUTS_HIP_EXPORT int wn_engine_create_with_datasets(wn_engine** out, int model
                                                       const double* model_params, const double* x, const double* y,
                                                       const int64_t* obs_offsets, int num_datasets, size_t num_chains,
                                                       const wn_config* cfg, WalnutpyError** err);
+/* A GROUPED data model (kUsesGroups; walnuts_amd/csrc/models/hier_glm.h): as wn_engine_create_with_data, plus the
+ * group of every observation, group [num_obs] (int32, host pointer, copied) with values in [0, num_groups).  x has
+ * P = num_params - num_groups - 1 columns (x [num_obs][P] row-major), stored on the device at the row stride
+ * 128 * ceil(P / 128).  Config errors, beside those of wn_engine_create_with_data: num_params != P + num_groups + 1
+ * with P >= 1 and num_groups >= 1, a group outside [0, num_groups), a grouped model created without groups (through
+ * wn_engine_create_with_data or _datasets), and groups for a model without kUsesGroups. */
+WALNUTS_HIP_EXPORT int wn_engine_create_with_grouped_data(wn_engine** out, int model, int num_params,
+                                                          const double* model_params, const double* x, const double* y,
+                                                          const int32_t* group, int num_groups, int num_obs,
+                                                          size_t num_chains, const wn_config* cfg, WalnutpyError** err);
+/* ... and several datasets of it (wn_engine_create_with_datasets): group [obs_offsets[num_datasets]] is sliced by
+ * obs_offsets like x and y; num_groups is shared by every dataset. */
+WALNUTS_HIP_EXPORT int wn_engine_create_with_grouped_datasets(wn_engine** out, int model, int num_params,
+                                                              const double* model_params, const double* x,
+                                                              const double* y, const int32_t* group, int num_groups,
+                                                              const int64_t* obs_offsets, int num_datasets,
+                                                              size_t num_chains, const wn_config* cfg,
+                                                              WalnutpyError** err);
 /* datasets of an engine (1 for one created without wn_engine_create_with_datasets) */
 WALNUTS_HIP_EXPORT int wn_engine_num_datasets(const wn_engine* e);
 WALNUTS_HIP_EXPORT void wn_engine_destroy(wn_engine* e);

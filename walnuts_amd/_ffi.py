@@ -92,6 +92,23 @@ SYMBOLS = [
      [_i32, _dp, _i32, _dp, _dp, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32,
       _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
       C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
+    # ... and for a grouped model: x, y, group (int32), num_groups, then num_obs or obs_offsets, num_datasets
+    ("walnutpie_sample_device_grouped", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
+    ("walnutpie_sample_device_grouped_resident", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
+    ("walnutpie_sample_device_grouped_datasets", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
+    ("walnutpie_sample_device_grouped_datasets_resident", _i32,
+     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
+      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
     ("walnutpie_sample_device_multi", _i32,
      [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
       _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
@@ -124,6 +141,10 @@ SYMBOLS = [
     ("wn_engine_create_with_data", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32, _sz, C.POINTER(Config), _errpp]),
     ("wn_engine_create_with_datasets", _i32,
      [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i64p, _i32, _sz, C.POINTER(Config), _errpp]),
+    ("wn_engine_create_with_grouped_data", _i32,
+     [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32p, _i32, _i32, _sz, C.POINTER(Config), _errpp]),
+    ("wn_engine_create_with_grouped_datasets", _i32,
+     [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32p, _i32, _i64p, _i32, _sz, C.POINTER(Config), _errpp]),
     ("wn_engine_num_datasets", _i32, [_vp]),
     ("wn_engine_destroy", None, [_vp]),
     ("wn_engine_eval", _i32, [_vp, _dp, _dp, _dp, _errpp]),

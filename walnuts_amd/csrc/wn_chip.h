@@ -97,6 +97,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   int n_lds;                                  // pool buffers [0, n_lds) live in LDS, the rest in the HBM arena
   const double* obs_x = nullptr;              // data models: the bound chain's observations (bind_data)
   const double* obs_yv = nullptr;
+  const int32_t* obs_gv = nullptr;            // grouped data models: the bound chain's group indices
   int obs_n = 0;
   int shift_parity = 0;                       // which copy of the shift scratch the last exchange used
 #if defined(WN_COUNT_POOL)
@@ -124,9 +125,30 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   // the engine's one block, or the chain's dataset of several (bind_data)
   __device__ __forceinline__ int num_obs() const { return obs_n; }
   __device__ __forceinline__ void load_row(int n, double (&x)[EPL]) const {
-    vload(obs_x + static_cast<long long>(n) * kDp, x);
+    if constexpr (uses_groups<Model>::value) {
+      // rows of P = num_params - num_groups - 1 columns at stride Dx = data_stride = 128 * ceil(P / 128): slot pair k
+      // holds columns [128 k, 128 k + 128), so pairs k >= Dx / 128 are zeros and issue no load (a wave-uniform test)
+      const int nx = P.data_stride / (2 * L);
+      const char* lb = lane_base(obs_x + static_cast<long long>(n) * P.data_stride);
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        if (k < nx) {
+          const v2f64 t = *reinterpret_cast<const v2f64*>(lb + k * (16 * L));
+          x[2 * k] = t[0];
+          x[2 * k + 1] = t[1];
+        } else {
+          x[2 * k] = 0.0;
+          x[2 * k + 1] = 0.0;
+        }
+      }
+    } else {
+      vload(obs_x + static_cast<long long>(n) * kDp, x);
+    }
   }
   __device__ __forceinline__ double obs_y(int n) const { return obs_yv[n]; }
+  // grouped data models (kUsesGroups): J, wave-uniform, and the group of observation n, in [0, J)
+  __device__ __forceinline__ int num_groups() const { return P.num_groups; }
+  __device__ __forceinline__ int obs_group(int n) const { return obs_gv[n]; }
   // Once per chain, before the model is evaluated for it: chain c of an engine with several datasets reads dataset
   // c / chains_per_dataset (the chain index is wave-uniform: one division and two scalar loads per chain, none per
   // row).  Row offsets are 64-bit, so a block beyond 4 GiB is addressed correctly.
@@ -135,12 +157,14 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
       if (P.chains_per_dataset > 0) {
         const int ds = c / P.chains_per_dataset;
         const long long first = P.data_offsets[ds];
-        obs_x = P.data_x + first * kDp;
+        obs_x = P.data_x + first * (uses_groups<Model>::value ? static_cast<long long>(P.data_stride) : kDp);
         obs_yv = P.data_y + first;
+        if constexpr (uses_groups<Model>::value) obs_gv = P.data_group + first;
         obs_n = static_cast<int>(P.data_offsets[ds + 1] - first);
       } else {
         obs_x = P.data_x;
         obs_yv = P.data_y;
+        if constexpr (uses_groups<Model>::value) obs_gv = P.data_group;
         obs_n = P.num_obs;
       }
     }
@@ -612,7 +636,11 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   // ------------------------------------------------------------------------------------
   // one MCMC transition (walnuts.hpp:520-563 wrapped as adaptive_walnuts.hpp:234-251 or walnuts.hpp:682-692)
   // ------------------------------------------------------------------------------------
-  __device__ void run(int chain_id) {
+  // Always inlined into the transition kernel: cold() reads Params through kernel_argument(), which is only the
+  // kernel's argument block inside the kernel's own body (wn_gfx950.h).  Left to the inliner, a model with a large
+  // eval() (models/hier_glm.h) made run() an out-of-line call, and every cold() field was read from the hidden
+  // arguments behind the block instead.
+  __device__ __forceinline__ void run(int chain_id) {
     WN_PHASE(kPhPrologue);
     this->refresh_ids();
 #if defined(WN_COUNT_POOL)

@@ -72,6 +72,11 @@ struct wn_engine {
   DevBuf<int64_t> data_offsets;
   int num_datasets = 1;
   int chains_per_dataset = 0;
+  // a grouped data model (kUsesGroups): the group of every row, J, and the narrower row stride Dx = 128 * ceil(P / 128)
+  // of its x (P = D - J - 1 columns); data_stride = Dp for every other model
+  DevBuf<int32_t> data_group;
+  int num_groups = 0;
+  int data_stride = 0;
   DevBuf<int32_t> min_micro, depth, rng_draws, failed_ext;
   DevBuf<int64_t> grad_evals;
   DevBuf<uint32_t> counter, error_flags;
@@ -285,9 +290,11 @@ struct wn_engine {
     P.data_x = data_x.p;
     P.data_y = data_y.p;
     P.num_obs = num_obs;
-    P.data_stride = Dp;
+    P.data_stride = data_stride;
     P.data_offsets = data_offsets.p;
     P.chains_per_dataset = chains_per_dataset;
+    P.data_group = data_group.p;
+    P.num_groups = num_groups;
     return P;
   }
 
@@ -432,6 +439,10 @@ struct HostData {
   int num_obs;
   const int64_t* offsets = nullptr;  // several datasets: dataset g is rows [offsets[g], offsets[g + 1])
   int num_datasets = 0;              // 0: one block shared by every chain
+  // a grouped data model (kUsesGroups): the group of every row, in [0, num_groups); x then has num_params -
+  // num_groups - 1 columns
+  const int32_t* group = nullptr;
+  int num_groups = 0;
 };
 
 void build_engine(wn_engine& e, int model, int num_params, const double* model_params, size_t num_chains,
@@ -455,6 +466,21 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
                                 "wn_engine_create_with_data (x [num_obs][num_params], y [num_obs])");
   if (!ops.uses_data && data != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
+  if (ops.uses_groups && data != nullptr && data->group == nullptr)
+    throw std::invalid_argument(std::string(ops.name) + " model reads a group per observation: create it with "
+                                "wn_engine_create_with_grouped_data (x [num_obs][num_params - num_groups - 1], y, group "
+                                "[num_obs] in [0, num_groups))");
+  if (!ops.uses_groups && data != nullptr && data->group != nullptr)
+    throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
+  // columns of x: num_params, or P = num_params - J - 1 for a grouped model
+  int cols = num_params;
+  if (ops.uses_groups && data != nullptr) {
+    const int J = data->num_groups;
+    if (J < 1 || num_params - J - 1 < 1)
+      throw std::invalid_argument("a grouped model needs num_params == P + num_groups + 1 with P >= 1 and num_groups >= 1, "
+                                  "got num_params " + std::to_string(num_params) + ", num_groups " + std::to_string(J));
+    cols = num_params - J - 1;
+  }
   size_t total_obs = 0;  // rows of the observation block
   if (data != nullptr && data->offsets != nullptr) {
     const int G = data->num_datasets;
@@ -476,19 +502,24 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   }
   if (data != nullptr) {
     if (data->x == nullptr || data->y == nullptr) throw std::invalid_argument("null data argument");
-    const size_t n = total_obs * static_cast<size_t>(num_params);
+    const size_t n = total_obs * static_cast<size_t>(cols);
     for (size_t i = 0; i < n; ++i)
       if (!std::isfinite(data->x[i])) throw std::invalid_argument("data x must be finite");
     for (size_t i = 0; i < total_obs; ++i)
       if (!std::isfinite(data->y[i])) throw std::invalid_argument("data y must be finite");
+    if (data->group != nullptr)
+      for (size_t i = 0; i < total_obs; ++i)
+        if (data->group[i] < 0 || data->group[i] >= data->num_groups)
+          throw std::invalid_argument("every group must be in [0, num_groups), observation " + std::to_string(i) + " has " +
+                                      std::to_string(data->group[i]));
     if (data->offsets == nullptr) {
-      ops.host_data(data->x, data->y, data->num_obs, num_params);
+      ops.host_data(data->x, data->y, data->num_obs, cols);
     } else {
       for (int g = 0; g < data->num_datasets; ++g) {
         const int64_t first = data->offsets[g];
         try {
-          ops.host_data(data->x + static_cast<size_t>(first) * num_params, data->y + first,
-                        static_cast<int>(data->offsets[g + 1] - first), num_params);
+          ops.host_data(data->x + static_cast<size_t>(first) * cols, data->y + first,
+                        static_cast<int>(data->offsets[g + 1] - first), cols);
         } catch (const std::invalid_argument& ex) {
           throw std::invalid_argument("dataset " + std::to_string(g) + ": " + ex.what());
         }
@@ -638,11 +669,18 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     HIP_OK(hipMemcpyAsync(e.model_params.p, mp.data(), mp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
     HIP_OK(hipStreamSynchronize(e.stream));
   }
+  // rows padded with zeros to the stride Dx: Dp, the layout of a theta row (lane tid's slot j holds coordinate index(j));
+  // for a grouped model 128 * ceil(P / 128), the slot pairs of theta that hold x's P columns
+  e.data_stride = ops.uses_groups ? 128 * ((cols + 127) / 128) : e.Dp;
+  if (data != nullptr && data->group != nullptr) {
+    e.num_groups = data->num_groups;
+    e.data_group.alloc(total_obs);
+    HIP_OK(hipMemcpyAsync(e.data_group.p, data->group, total_obs * sizeof(int32_t), hipMemcpyHostToDevice, e.stream));
+  }
   if (data != nullptr && data->offsets == nullptr) {
-    // rows padded to Dp with zeros: the layout of a theta row (lane tid's slot j holds coordinate index(j))
-    const size_t N = static_cast<size_t>(data->num_obs);
-    std::vector<double> xp(N * static_cast<size_t>(e.Dp), 0.0);
-    for (size_t n = 0; n < N; ++n) std::memcpy(&xp[n * e.Dp], data->x + n * num_params, sizeof(double) * num_params);
+    const size_t N = static_cast<size_t>(data->num_obs), Dx = static_cast<size_t>(e.data_stride);
+    std::vector<double> xp(N * Dx, 0.0);
+    for (size_t n = 0; n < N; ++n) std::memcpy(&xp[n * Dx], data->x + n * cols, sizeof(double) * cols);
     e.data_x.alloc(xp.size());
     e.data_y.alloc(N);
     e.num_obs = data->num_obs;
@@ -652,7 +690,7 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   } else if (data != nullptr) {
     // the datasets one after another, rows padded as above; the padded copy goes up in slices of at most 64 MiB (a
     // block of many datasets may be larger than what is sensible to double in host memory)
-    const size_t N = total_obs, Dp = static_cast<size_t>(e.Dp);
+    const size_t N = total_obs, Dp = static_cast<size_t>(e.data_stride);  // (the row stride Dx)
     const int G = data->num_datasets;
     e.data_x.alloc(N * Dp);
     e.data_y.alloc(N);
@@ -665,7 +703,7 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     for (size_t n0 = 0; n0 < N; n0 += slice) {
       const size_t rows = std::min(slice, N - n0);
       for (size_t n = 0; n < rows; ++n)
-        std::memcpy(&xp[n * Dp], data->x + (n0 + n) * num_params, sizeof(double) * num_params);
+        std::memcpy(&xp[n * Dp], data->x + (n0 + n) * cols, sizeof(double) * cols);
       HIP_OK(hipMemcpyAsync(e.data_x.p + n0 * Dp, xp.data(), rows * Dp * sizeof(double), hipMemcpyHostToDevice, e.stream));
       HIP_OK(hipStreamSynchronize(e.stream));  // (before the staging slice is refilled)
     }
@@ -711,9 +749,11 @@ void run_init(wn_engine& e, bool pos, bool masses, bool step, double scale, doub
   Q.data_x = e.data_x.p;
   Q.data_y = e.data_y.p;
   Q.num_obs = e.num_obs;
-  Q.data_stride = e.Dp;
+  Q.data_stride = e.data_stride;
   Q.data_offsets = e.data_offsets.p;
   Q.chains_per_dataset = e.chains_per_dataset;
+  Q.data_group = e.data_group.p;
+  Q.num_groups = e.num_groups;
   const int grid = e.geo.mem ? e.grid : static_cast<int>(std::min<size_t>(e.C, static_cast<size_t>(e.num_cus) * 8));
   wn::launch_init(e.model, e.geo, grid, wn::transition_smem_bytes(e.geo.nw, 0, e.Dp), e.stream, Q);
   HIP_OK(hipGetLastError());
@@ -906,6 +946,36 @@ int wn_engine_create_with_datasets(wn_engine** out, int model, int num_params, c
     *out = e.release();
   });
 }
+int wn_engine_create_with_grouped_data(wn_engine** out, int model, int num_params, const double* model_params,
+                                       const double* x, const double* y, const int32_t* group, int num_groups, int num_obs,
+                                       size_t num_chains, const wn_config* cfg, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (out == nullptr || cfg == nullptr || group == nullptr) throw std::invalid_argument("null argument");
+    HostData data{x, y, num_obs};
+    data.group = group;
+    data.num_groups = num_groups;
+    auto e = std::make_unique<wn_engine>();
+    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
+    *out = e.release();
+  });
+}
+int wn_engine_create_with_grouped_datasets(wn_engine** out, int model, int num_params, const double* model_params,
+                                           const double* x, const double* y, const int32_t* group, int num_groups,
+                                           const int64_t* obs_offsets, int num_datasets, size_t num_chains,
+                                           const wn_config* cfg, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (out == nullptr || cfg == nullptr || obs_offsets == nullptr || group == nullptr)
+      throw std::invalid_argument("null argument");
+    HostData data{x, y, 0};
+    data.offsets = obs_offsets;
+    data.num_datasets = num_datasets;
+    data.group = group;
+    data.num_groups = num_groups;
+    auto e = std::make_unique<wn_engine>();
+    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
+    *out = e.release();
+  });
+}
 int wn_engine_num_datasets(const wn_engine* e) { return e->num_datasets; }
 void wn_engine_destroy(wn_engine* e) { delete e; }
 
@@ -934,9 +1004,11 @@ int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* 
     Q.data_x = e->data_x.p;
     Q.data_y = e->data_y.p;
     Q.num_obs = e->num_obs;
-    Q.data_stride = e->Dp;
+    Q.data_stride = e->data_stride;
     Q.data_offsets = e->data_offsets.p;
     Q.chains_per_dataset = e->chains_per_dataset;
+    Q.data_group = e->data_group.p;
+    Q.num_groups = e->num_groups;
     Q.logp_out = lp.p;
     Q.grad_out = grad.p;
     const int grid = e->geo.mem ? e->grid : static_cast<int>(std::min<size_t>(C, static_cast<size_t>(e->num_cus) * 8));

@@ -202,6 +202,9 @@ __device__ __forceinline__ int wave_in_workgroup() { return __builtin_amdgcn_rea
 // The kernel's single by-value argument struct, read back from the kernel-argument segment behind an optimisation
 // barrier: fields used once or twice per transition are then fetched where they are used (s_load) instead of being
 // loaded at the kernel entry and held -- or spilled to VGPR lanes -- for the whole kernel.
+// Valid only in code inlined into the kernel itself: in an out-of-line device function the segment pointer the
+// compiler hands over is the implicit-argument pointer (past the explicit arguments), so every caller of this on the
+// way from the kernel is __forceinline__.
 template <class T>
 __device__ __forceinline__ const __attribute__((address_space(4))) T& kernel_argument(const T&) {
   typedef const __attribute__((address_space(4))) T CT;

@@ -31,6 +31,8 @@ struct InitParams {
   int32_t data_stride;
   const int64_t* data_offsets;
   int32_t chains_per_dataset;
+  const int32_t* data_group;
+  int32_t num_groups;
   // eval_kernel (wn_engine_eval): the model's log density [C] and gradient [C][Dp] at theta
   double* logp_out;
   double* grad_out;
@@ -51,6 +53,8 @@ __global__ __launch_bounds__(64 * NW) void init_kernel(const InitParams Q) {
   P.data_stride = Q.data_stride;
   P.data_offsets = Q.data_offsets;
   P.chains_per_dataset = Q.chains_per_dataset;
+  P.data_group = Q.data_group;
+  P.num_groups = Q.num_groups;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;
@@ -161,6 +165,8 @@ __global__ __launch_bounds__(64 * NW) void eval_kernel(const InitParams Q) {
   P.data_stride = Q.data_stride;
   P.data_offsets = Q.data_offsets;
   P.chains_per_dataset = Q.chains_per_dataset;
+  P.data_group = Q.data_group;
+  P.num_groups = Q.num_groups;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;

@@ -61,6 +61,11 @@
 //     // geometries, a data model without data and data for a model without this member (`config` errors).
 //     static constexpr bool kUsesData = true;
 //     static void host_data(const double* x, const double* y, int num_obs, int num_params);  // optional checks (throw)
+//     // ... and, on top of kUsesData, a GROUP per observation (int32 in [0, J), copied beside y;
+//     // wn_engine_create_with_grouped_data / walnutpie_sample_device_grouped*): x then has P = num_params - J - 1
+//     // columns, stored at the narrower row stride Dx = 128 * ceil(P / 128) (host_data's last argument is P).
+//     // wn_engine_create refuses a grouped model without groups and groups for a model without this member.
+//     static constexpr bool kUsesGroups = true;
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -81,6 +86,11 @@
 //                                             cx.index(j), zero beyond num_params (a row is laid out like theta and
 //                                             loads with the same 16-byte pair loads); n wave-uniform, 0 <= n < num_obs
 //   cx.obs_y(n)                               y[n] (0 <= n < num_obs)
+// ... and for grouped data models only (kUsesGroups):
+//   cx.num_groups()                           J, wave-uniform
+//   cx.obs_group(n)                           the group of observation n, in [0, J) (0 <= n < num_obs)
+//   (cx.load_row then fills slot pairs k < Dx / 128 -- columns [128 k, 128 k + 128) -- and zeros the rest without
+//   loading them; a flat model's rows keep the stride Dp and its loads)
 // The wavefront primitives of the platform layer (wave_sum_packed, lane_value, set_lane, uni, ...: wn_gfx950.h, with
 // the same association order under the CPU emulation) are available to eval(); models/glm.h uses them to reduce two
 // rows' dot products per butterfly.
@@ -90,13 +100,15 @@
 //
 // Registration is a five-line translation unit, wn_kernels_<name>.hip, that the Makefile picks up by its name:
 //   #include "models/my_model.h"
-//   #define WN_MODEL_ID 6                 // 0-5 are taken (std_normal, diag_normal, funnel, rw1, linear_regression,
-//                                         //   logistic_regression); < 64
+//   #define WN_MODEL_ID 6                 // 0-5 and 15-18 are taken (std_normal, diag_normal, funnel, rw1,
+//                                         //   linear_regression, logistic_regression; hier_linear_regression,
+//                                         //   hier_logistic_regression and their _centered forms); < 64
 //   #define WN_MODEL_TAG my_model         // wn_model_id("my_model") finds it at run time
 //   #define WN_MODEL_TYPE wn::MyModel
 //   #include "wn_kernels.inc"
 // models/rw1.h is a complete example (the reference's AR(1) density with a neighbour-coupled gradient); models/glm.h
-// one of a model conditioned on data (Bayesian linear and logistic regression).
+// one of a model conditioned on data (Bayesian linear and logistic regression); models/hier_glm.h one with a group
+// channel (hierarchical regression with varying intercepts).
 #pragma once
 
 #include "wn_devmath.h"

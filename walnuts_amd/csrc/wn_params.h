@@ -102,6 +102,10 @@ struct Params {
   // [data_offsets[g], data_offsets[g + 1]) of data_x / data_y; chains_per_dataset = 0: one block shared by every chain
   const int64_t* data_offsets;  // [G + 1]
   int32_t chains_per_dataset;
+  // grouped data models (kUsesGroups): the group of every observation, in [0, num_groups), sliced like data_y.  Their
+  // rows are narrower than theta: data_stride = 128 * ceil(P / 128) doubles for P = num_params - num_groups - 1 columns
+  const int32_t* data_group;  // [num_obs] (null for other models)
+  int32_t num_groups;
 };
 
 enum : uint32_t {

@@ -847,6 +847,11 @@ struct SampleData {
   bool several = false;              // walnutpie_sample_device_datasets*: the two fields below describe the datasets
   const int64_t* offsets = nullptr;  // dataset g is rows [offsets[g], offsets[g + 1])
   int num_datasets = 0;
+  // walnutpie_sample_device_grouped*: the group of every row (a grouped model: kUsesGroups), copied by
+  // wn_engine_create_with_grouped_data / _datasets
+  bool grouped = false;
+  const int32_t* group = nullptr;
+  int num_groups = 0;
 };
 struct Mode {
   bool reference_streams = false;            // walnutpie_sample_device_reference_streams
@@ -1113,7 +1118,15 @@ void run_shard(const Model& m, const SampleArgs& a, const Mode& mode, const Plan
   // started once the device allocations are done -- see below)
   std::unique_ptr<Prefault> populate;
   EngineGuard guard;
-  if (mode.data != nullptr && mode.data->several) {
+  if (mode.data != nullptr && mode.data->grouped && mode.data->several) {
+    WN_CALL(wn_engine_create_with_grouped_datasets(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
+                                                   mode.data->group, mode.data->num_groups, mode.data->offsets,
+                                                   mode.data->num_datasets, C, &plan.cfg, &call_err_));
+  } else if (mode.data != nullptr && mode.data->grouped) {
+    WN_CALL(wn_engine_create_with_grouped_data(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
+                                               mode.data->group, mode.data->num_groups, mode.data->num_obs, C,
+                                               &plan.cfg, &call_err_));
+  } else if (mode.data != nullptr && mode.data->several) {
     WN_CALL(wn_engine_create_with_datasets(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
                                            mode.data->offsets, mode.data->num_datasets, C, &plan.cfg, &call_err_));
   } else if (mode.data != nullptr) {
@@ -1447,6 +1460,49 @@ extern "C" int walnutpie_sample_device_datasets_resident(int model, const double
                                                          wn_chains** chains_out, WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out};
   const SampleData data{x, y, 0, true, obs_offsets, num_datasets};
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
+}
+// ... and for a grouped model (walnuts_amd/csrc/models/hier_glm.h: group, num_groups after y), one block or several
+extern "C" int walnutpie_sample_device_grouped(int model, const double* model_params, int num_params, const double* x,
+                                               const double* y, const int32_t* group, int num_groups, int num_obs,
+                                               WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
+  SampleData data{x, y, num_obs};
+  data.grouped = true;
+  data.group = group;
+  data.num_groups = num_groups;
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
+}
+extern "C" int walnutpie_sample_device_grouped_resident(int model, const double* model_params, int num_params,
+                                                        const double* x, const double* y, const int32_t* group,
+                                                        int num_groups, int num_obs, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
+                                                        wn_chains** chains_out, WalnutpyError** err) {
+  const ResidentRequest req{thin, chains_out};
+  SampleData data{x, y, num_obs};
+  data.grouped = true;
+  data.group = group;
+  data.num_groups = num_groups;
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
+}
+extern "C" int walnutpie_sample_device_grouped_datasets(int model, const double* model_params, int num_params,
+                                                        const double* x, const double* y, const int32_t* group,
+                                                        int num_groups, const int64_t* obs_offsets, int num_datasets,
+                                                        WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
+  SampleData data{x, y, 0, true, obs_offsets, num_datasets};
+  data.grouped = true;
+  data.group = group;
+  data.num_groups = num_groups;
+  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
+}
+extern "C" int walnutpie_sample_device_grouped_datasets_resident(int model, const double* model_params, int num_params,
+                                                                 const double* x, const double* y, const int32_t* group,
+                                                                 int num_groups, const int64_t* obs_offsets,
+                                                                 int num_datasets, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
+                                                                 wn_chains** chains_out, WalnutpyError** err) {
+  const ResidentRequest req{thin, chains_out};
+  SampleData data{x, y, 0, true, obs_offsets, num_datasets};
+  data.grouped = true;
+  data.group = group;
+  data.num_groups = num_groups;
   return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
 }
 extern "C" int walnutpie_sample_device_multi(int model, const double* model_params, int num_params,

@@ -967,6 +967,12 @@ template <class M, class = void>
 struct uses_data : std::false_type {};
 template <class M>
 struct uses_data<M, std::enable_if_t<M::kUsesData>> : std::true_type {};
+// ... and a data model that also reads a group index per observation (kUsesGroups: cx.num_groups() / obs_group(), rows
+// of P = num_params - num_groups - 1 columns at the narrower stride Params::data_stride)
+template <class M, class = void>
+struct uses_groups : std::false_type {};
+template <class M>
+struct uses_groups<M, std::enable_if_t<M::kUsesGroups>> : std::true_type {};
 template <class M, bool Elementwise = M::kElementwise>
 struct StreamTraits {
   static constexpr bool kTwoPass = false, kHasSums = false, kHalo = false;

@@ -162,6 +162,9 @@ def walnuts_device(
     ``x`` of shape (num_obs, num_params) and ``y`` of shape (num_obs,); copied to the device once.  One device only:
     not with ``devices`` or ``reference_streams``.
 
+    ``data=(x, y, group)`` (walnutpie_sample_device_grouped / _grouped_resident): a grouped model (MODEL_HIER_*), x of
+    shape (num_obs, P), groups in [0, J), J = num_params - P - 1; ``datasets=`` then takes triples (x, y, group).
+
     ``datasets=[(x0, y0), (x1, y1), ...]`` (walnutpie_sample_device_datasets / _datasets_resident): G datasets of the
     same model and prior, fitted in one run.  ``num_chains`` (the total) must be a multiple k of G; chains
     [g*k, (g+1)*k) are conditioned on dataset g, and the results list is per chain as usual.  Warmup and sampling stop
@@ -203,7 +206,16 @@ def walnuts_device(
     if seed is None:
         seed = int(np.random.randint(0, 2**32 - 1, dtype=np.uint32))
     data_args = ()
-    if data is not None:
+    grouped = False
+    from .engine import _is_grouped
+
+    if data is not None and _is_grouped(data):
+        from .engine import _grouped_arrays
+
+        x, y, grp, J = _grouped_arrays(data, num_params)
+        grouped = True
+        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), grp.ctypes.data_as(_ffi._i32p), J, y.size)
+    elif data is not None:
         from .engine import _data_arrays
 
         x, y = _data_arrays(data, num_params)
@@ -212,10 +224,11 @@ def walnuts_device(
     if datasets is not None:
         from .engine import _datasets_arrays
 
-        x, y, offsets = _datasets_arrays(datasets, num_params)
+        x, y, offsets, grp, J = _datasets_arrays(datasets, num_params)
         num_datasets = offsets.size - 1
-        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), offsets.ctypes.data_as(_ffi._i64p),
-                     num_datasets)
+        grouped = grp is not None
+        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp)) + (
+            (grp.ctypes.data_as(_ffi._i32p), J) if grouped else ()) + (offsets.ctypes.data_as(_ffi._i64p), num_datasets)
     mp = None if model_params is None else np.ascontiguousarray(np.asarray(model_params, dtype=np.float64))
     if mp is not None and mp.size != num_params:
         raise ValueError("model_params must have num_params entries")
@@ -251,8 +264,13 @@ def walnuts_device(
         tail = (refresh, cb, thin, C.byref(chains_handle), C.byref(err))
     if data is not None:
         entry = lib.walnutpie_sample_device_data_resident if keep_on_device else lib.walnutpie_sample_device_data
+        if grouped:
+            entry = lib.walnutpie_sample_device_grouped_resident if keep_on_device else lib.walnutpie_sample_device_grouped
     if datasets is not None:
         entry = lib.walnutpie_sample_device_datasets_resident if keep_on_device else lib.walnutpie_sample_device_datasets
+        if grouped:
+            entry = (lib.walnutpie_sample_device_grouped_datasets_resident if keep_on_device
+                     else lib.walnutpie_sample_device_grouped_datasets)
     if devices is not None:
         dev = (C.c_int * len(devices))(*[int(d) for d in devices])
         entry = lib.walnutpie_sample_device_multi

@@ -17,6 +17,12 @@ from . import _ffi
 MODEL_STD_NORMAL, MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_RW1 = 0, 1, 2, 3
 # models conditioned on data (walnuts_amd/csrc/models/glm.h): params = the prior variances, data = (x, y)
 MODEL_LINEAR_REGRESSION, MODEL_LOGISTIC_REGRESSION = 4, 5
+# hierarchical regression with varying intercepts by group (walnuts_amd/csrc/models/hier_glm.h): theta = [beta (P) |
+# group effects (J) | log tau], params = [prior variances of beta (P) | 1 (J, reserved) | sigma_tau], data = (x, y, group)
+# with x of P = num_params - J - 1 columns and group in [0, J); non-centered (u = z) and centered (u = a)
+# (ids 6-14 stay free for models of one's own: the out-of-tree examples and tests take ids there)
+MODEL_HIER_LINEAR_REGRESSION, MODEL_HIER_LOGISTIC_REGRESSION = 15, 16
+MODEL_HIER_LINEAR_REGRESSION_CENTERED, MODEL_HIER_LOGISTIC_REGRESSION_CENTERED = 17, 18
 _dp = _ffi._dp
 
 
@@ -63,33 +69,80 @@ def _data_arrays(data, num_params: int):
     return x, y
 
 
+def _grouped_arrays(data, num_params: int):
+    """(x, y, group) of a grouped model (kUsesGroups) as contiguous arrays: x (num_obs, P) float64, y (num_obs,)
+    float64, group (num_obs,) int32, and J = num_params - P - 1 (the engine checks J >= 1, P >= 1 and the range)."""
+    x, y, group = data
+    x, y = _f64(x), _f64(y)
+    if x.ndim != 2:
+        raise ValueError(f"data x must have shape (num_obs, P), got {x.shape}")
+    if y.ndim != 1 or y.shape[0] != x.shape[0]:
+        raise ValueError(f"data y must have shape ({x.shape[0]},), got {y.shape}")
+    if x.shape[0] < 1:
+        raise ValueError("data needs at least one observation")
+    g = np.asarray(group)
+    if g.shape != y.shape:
+        raise ValueError(f"data group must have shape ({x.shape[0]},), got {g.shape}")
+    if g.dtype.kind not in "iu":
+        raise ValueError(f"data group must hold integers, got dtype {g.dtype}")
+    if g.size and (g.min() < np.iinfo(np.int32).min or g.max() > np.iinfo(np.int32).max):
+        raise ValueError("every group must be in [0, num_groups)")
+    return x, y, np.ascontiguousarray(g, dtype=np.int32), num_params - x.shape[1] - 1
+
+
+def _is_grouped(data) -> bool:
+    """data is an (x, y, group) triple rather than an (x, y) pair"""
+    try:
+        return len(data) == 3
+    except TypeError:
+        return False
+
+
 def _datasets_arrays(datasets, num_params: int):
     """Several datasets [(x0, y0), (x1, y1), ...] as one block: x (rows, num_params) and y (rows,) stacked in order,
-    and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1])."""
+    and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1]).  Triples (x, y, group) of a grouped
+    model give x (rows, P) and a fourth and fifth entry: the stacked int32 groups and J; pairs give None, 0 there."""
     try:
-        pairs = [_data_arrays(d, num_params) for d in datasets]
+        items = list(datasets)
     except TypeError:
-        raise ValueError("datasets must be a sequence of (x, y) pairs") from None
-    if not pairs:
+        raise ValueError("datasets must be a sequence of (x, y) pairs or (x, y, group) triples") from None
+    if not items:
         raise ValueError("datasets needs at least one (x, y) pair")
-    offsets = np.zeros(len(pairs) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum([y.size for _, y in pairs])
-    x = np.ascontiguousarray(np.concatenate([x for x, _ in pairs], axis=0))
-    y = np.ascontiguousarray(np.concatenate([y for _, y in pairs]))
-    return x, y, offsets
+    grouped = _is_grouped(items[0])
+    if any(_is_grouped(d) != grouped for d in items):
+        raise ValueError("datasets must be all (x, y) pairs or all (x, y, group) triples")
+    if grouped:
+        parts = [_grouped_arrays(d, num_params) for d in items]
+        if len({p[0].shape[1] for p in parts}) != 1:
+            raise ValueError("every dataset's x must have the same number of columns")
+    else:
+        try:
+            parts = [_data_arrays(d, num_params) for d in items]
+        except TypeError:
+            raise ValueError("datasets must be a sequence of (x, y) pairs") from None
+    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([p[1].size for p in parts])
+    x = np.ascontiguousarray(np.concatenate([p[0] for p in parts], axis=0))
+    y = np.ascontiguousarray(np.concatenate([p[1] for p in parts]))
+    if grouped:
+        return x, y, offsets, np.ascontiguousarray(np.concatenate([p[2] for p in parts])), parts[0][3]
+    return x, y, offsets, None, 0
 
 
 class DeviceEngine:
     def __init__(self, model: int, dim: int, num_chains: int, cfg: Optional[_ffi.Config] = None,
                  params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None, datasets=None):
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
-        (num_obs, dim) and y of shape (num_obs,); copied to the device once.
+        (num_obs, dim) and y of shape (num_obs,); copied to the device once.  `data=(x, y, group)` for a grouped model
+        (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
+        [0, J) with J = dim - P - 1 (wn_engine_create_with_grouped_data).
 
         `datasets=[(x0, y0), (x1, y1), ...]` instead: G datasets of the same model and prior (sizes may differ), fitted
         side by side (wn_engine_create_with_datasets).  num_chains must be a multiple k of G; chains [g*k, (g+1)*k)
         are conditioned on dataset g and evolve exactly as chains 0..k-1 of an engine built with data=(xg, yg) and
         seeded with chain_offset = g*k.  Per-dataset statistics: rhat_per_dataset(), warmup_spread_per_dataset();
-        init_masses_from_grad(average=True) averages over each dataset's chains."""
+        init_masses_from_grad(average=True) averages over each dataset's chains.  A grouped model takes triples
+        [(x0, y0, g0), ...] with the same number of columns in every x (wn_engine_create_with_grouped_datasets)."""
         if data is not None and datasets is not None:
             raise ValueError("data and datasets are mutually exclusive")
         self.lib = _ffi.load_library(lib_path)
@@ -102,12 +155,23 @@ class DeviceEngine:
         pp = None if p is None else p.ctypes.data_as(_dp)
         self._several = datasets is not None
         if datasets is not None:
-            x, y, off = _datasets_arrays(datasets, self.D)
-            rc = self.lib.wn_engine_create_with_datasets(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
-                                                         y.ctypes.data_as(_dp), off.ctypes.data_as(_ffi._i64p),
-                                                         off.size - 1, num_chains, C.byref(self.cfg), C.byref(err))
+            x, y, off, grp, J = _datasets_arrays(datasets, self.D)
+            if grp is not None:
+                rc = self.lib.wn_engine_create_with_grouped_datasets(
+                    C.byref(h), model, dim, pp, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp),
+                    grp.ctypes.data_as(_ffi._i32p), J, off.ctypes.data_as(_ffi._i64p), off.size - 1, num_chains,
+                    C.byref(self.cfg), C.byref(err))
+            else:
+                rc = self.lib.wn_engine_create_with_datasets(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
+                                                             y.ctypes.data_as(_dp), off.ctypes.data_as(_ffi._i64p),
+                                                             off.size - 1, num_chains, C.byref(self.cfg), C.byref(err))
         elif data is None:
             rc = self.lib.wn_engine_create(C.byref(h), model, dim, pp, num_chains, C.byref(self.cfg), C.byref(err))
+        elif _is_grouped(data):
+            x, y, grp, J = _grouped_arrays(data, self.D)
+            rc = self.lib.wn_engine_create_with_grouped_data(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
+                                                             y.ctypes.data_as(_dp), grp.ctypes.data_as(_ffi._i32p), J,
+                                                             y.size, num_chains, C.byref(self.cfg), C.byref(err))
         else:
             x, y = _data_arrays(data, self.D)
             rc = self.lib.wn_engine_create_with_data(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
