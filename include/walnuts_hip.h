@@ -149,7 +149,13 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
 /* walnutpie_sample_device / _resident for a model conditioned on data (walnuts_amd/csrc/wn_model_api.h, kUsesData:
  * MODEL_LINEAR_REGRESSION, MODEL_LOGISTIC_REGRESSION, or a model of your own): x [num_obs][num_params] row-major and
  * y [num_obs], host pointers, checked and copied to the device once (not retained).  Everything else as the calls
- * above.  One device only: the multi-device and reference-stream entry points take no data. */
+ * above.  One device only: the multi-device and reference-stream entry points take no data.
+ * Count models and an estimated noise level (walnuts_amd/csrc/models/glm.h, glm_scale.h) use the same calls:
+ * poisson_regression (24) as linear_regression; neg_binomial_regression (25, NB2: kappa = exp(s), Var y = mu + kappa
+ * mu^2) and linear_regression_sigma (26, noise sigma = exp(s)) end theta with the log scale s, so their x has
+ * num_params - 1 columns and model_params is [prior variances (num_params - 1) | sigma_0], the half-normal scale of
+ * exp(s).  The count models refuse a y that is not a finite non-negative integer (`config`).  hier_poisson_regression
+ * (27) and its _centered form (28) take the grouped calls below. */
 WALNUTS_HIP_EXPORT int walnutpie_sample_device_data(
     int model, const double* model_params, int num_params, const double* x, const double* y, int num_obs,
     const double* inits, size_t num_chains,
@@ -208,7 +214,8 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_datasets_resident(
     double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
     int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
     int thin, wn_chains** chains_out, WalnutpyError** err);
-/* The same four calls for a GROUPED model (kUsesGroups: hier_linear_regression, hier_logistic_regression and their
+/* The same four calls for a GROUPED model (kUsesGroups: hier_linear_regression, hier_logistic_regression,
+ * hier_poisson_regression and their
  * _centered forms, walnuts_amd/csrc/models/hier_glm.h): group [rows] (int32, every entry in [0, num_groups)) and
  * num_groups after y; x then has P = num_params - num_groups - 1 columns (P >= 1, num_groups >= 1).  With several
  * datasets the groups are sliced by obs_offsets like x and y, and num_groups is shared (a dataset may leave groups
@@ -370,6 +377,11 @@ WALNUTS_HIP_EXPORT void wn_default_config(wn_config* cfg);
  * (walnuts_amd/csrc/wn_model_api.h; INTEGRATION.md "Adding a device model").  -> the id registered under `name`
  * ("std_normal" 0, "diag_normal" 1, "funnel" 2, "rw1" 3, ...), or -1. */
 WALNUTS_HIP_EXPORT int wn_model_id(const char* name);
+/* The number of columns of x that a data model reads at num_params (and, for a grouped model, num_groups): num_params
+ * for the flat models, num_params - 1 for a model with a scale parameter (kScaleParam: neg_binomial_regression,
+ * linear_regression_sigma), num_params - num_groups - 1 for a grouped model.  -> -1 for an id no data model holds, and
+ * for a grouped model with num_groups < 1. */
+WALNUTS_HIP_EXPORT int wn_model_data_columns(int model, int num_params, int num_groups);
 /* Version of the counter-based random streams of this build (the map (seed, chain, transition, index) -> variate,
  * csrc/wn_devmath.h): results at a fixed seed are reproducible within one version only.  A caller that stores draws
  * or resumes a run records it beside the seed; walnuts_amd writes it into every result and bench line.
@@ -627,6 +639,10 @@ WALNUTS_HIP_EXPORT int wn_lanes_for_model_dim(int model, int num_params, int wav
 /* (internal, for the tests) the kernels' range-free square root (csrc/wn_devmath.h sqrt_normal) evaluated on the device
  * for n host arguments; checked != 0: the variant that patches 0 / inf back in.  -> 0, or -1 */
 WALNUTS_HIP_EXPORT int wn_internal_sqrt_probe(const double* x, double* y, size_t n, int checked);
+/* (internal, for the tests) the count models' maths (csrc/wn_devmath.h) evaluated on the device for n host arguments:
+ * fn 0 dlog1p(x), 1 dsoftplus(x), 2 dlgamma_diff(x, phi) = lgamma(x + phi) - lgamma(phi), 3 ddigamma_diff(x, phi) =
+ * psi(x + phi) - psi(phi) (phi is read for fn 2 and 3 only, but must hold n doubles).  -> 0, or -1 */
+WALNUTS_HIP_EXPORT int wn_internal_count_math_probe(const double* x, const double* phi, double* y, size_t n, int fn);
 WALNUTS_HIP_EXPORT void wn_internal_reference_normals(unsigned int seed, unsigned int stream, size_t num_chains,
                                                       size_t count_per_chain, int fresh_per_chain, double scale,
                                                       double* out);

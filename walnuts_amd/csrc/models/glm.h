@@ -1,12 +1,15 @@
 // models/glm.h -- Bayesian generalised linear models on an observation block the engine keeps in HBM (wn_model_api.h,
-// kUsesData): linear regression (unit-variance normal noise) and logistic regression, one template over the link.
+// kUsesData): linear regression (unit-variance normal noise), logistic regression and Poisson regression, one template
+// over the link.
 //
 //   eta = X theta,  prior theta_i ~ normal(0, s_i^2)  (model_params: the prior variances s^2)
 //   linear_regression:    logp = -1/2 sum_n (y_n - eta_n)^2             - 1/2 sum_i theta_i^2 / s_i^2
 //                         grad = X^T (y - eta)                            - theta / s^2
 //   logistic_regression:  logp = sum_n (y_n eta_n - softplus(eta_n))     - 1/2 sum_i theta_i^2 / s_i^2
 //                         grad = X^T (y - sigmoid(eta))                   - theta / s^2
-// (constants dropped.  Another noise level sigma for the linear model: pass x / sigma and y / sigma.)
+//   poisson_regression:   logp = sum_n (y_n eta_n - exp(eta_n))           - 1/2 sum_i theta_i^2 / s_i^2
+//                         grad = X^T (y - exp(eta))                       - theta / s^2
+// (constants dropped.  A linear model with an unknown noise level sigma, and the negative binomial: models/glm_scale.h.)
 //
 // One pass over X per gradient evaluation.  The chain's lane `tid` holds EPL coordinates of theta, and row n of X is
 // laid out the same way, so a row is EPL / 2 16-byte loads per lane and its product with theta is EPL lane-local
@@ -62,6 +65,34 @@ struct LogitLink {
     if (!(y == 0.0 || y == 1.0)) throw std::invalid_argument("logistic_regression needs every y in {0, 1}");
   }
 };
+
+struct LogLink {
+  // Poisson: r = y - exp(eta); ll += y eta - exp(eta) (-lgamma(y + 1) dropped).  exp(eta) overflows to inf beyond
+  // eta ~ 709.78: the term is then non-finite and the trajectory treats it as every non-finite energy.
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static double term(double eta, double y, double& r, double ll, const Tab& tab) {
+    const double mu = wnd::dexp(eta, tab);
+    r = y - mu;
+    return Cx::mad(y, eta, ll) - mu;
+  }
+  static void check_y(double y) { check_count(y, "Poisson regression"); }
+  // a count: finite, >= 0 and integer-valued
+  static void check_count(double y, const char* model) {
+    if (!(std::isfinite(y) && y >= 0.0 && y == std::floor(y)))
+      throw std::invalid_argument(std::string(model) + " needs every y to be a count (finite, >= 0, integer-valued), got " +
+                                  std::to_string(y));
+  }
+};
+
+// the value of coordinate c (wave-uniform) of a vector laid out like theta, in every lane (one wavefront)
+template <int EPL>
+__device__ __forceinline__ double coord_value(const double (&v)[EPL], int c) {
+  const int slot = 2 * (c >> 7) + (c & 1);
+  double mine = 0.0;
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) mine = j == slot ? v[j] : mine;
+  return lane_value(mine, (c >> 1) & 63);
+}
 
 template <class Link>
 struct GlmModel {
@@ -150,5 +181,6 @@ struct GlmModel {
 
 using LinearRegressionModel = GlmModel<IdentityLink>;
 using LogisticRegressionModel = GlmModel<LogitLink>;
+using PoissonRegressionModel = GlmModel<LogLink>;
 
 }  // namespace wn

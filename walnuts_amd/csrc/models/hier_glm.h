@@ -1,6 +1,6 @@
 // models/hier_glm.h -- hierarchical (multilevel) regression with varying intercepts by group, on an observation block
-// with a group channel (wn_model_api.h, kUsesData + kUsesGroups): linear and logistic, each non-centered and centered,
-// one template over the link (models/glm.h) and the parameterization.
+// with a group channel (wn_model_api.h, kUsesData + kUsesGroups): linear, logistic and Poisson, each non-centered and
+// centered, one template over the link (models/glm.h) and the parameterization.
 //
 //   theta = [beta_0 .. beta_{P-1} | u_0 .. u_{J-1} | s],  tau = exp(s),  g(n) in [0, J) the group of observation n
 //   model_params [P + J + 1]: the prior variances s2_i of beta, J reserved entries (1), the half-normal scale sigma_tau
@@ -47,14 +47,10 @@ struct HierGlmModel {
   template <int EPL>
   static constexpr int kBlock = GlmModel<Link>::template kBlock<EPL>;
 
-  // the value of coordinate c (wave-uniform) of a vector laid out like theta, in every lane (one wavefront)
+  // the value of coordinate c (wave-uniform) of a vector laid out like theta, in every lane (glm.h)
   template <int EPL>
   __device__ __forceinline__ static double coord(const double (&v)[EPL], int c) {
-    const int slot = 2 * (c >> 7) + (c & 1);
-    double mine = 0.0;
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) mine = j == slot ? v[j] : mine;
-    return lane_value(mine, (c >> 1) & 63);
+    return coord_value(v, c);
   }
 
   template <int EPL, class Cx>
@@ -195,5 +191,7 @@ using HierLinearRegressionModel = HierGlmModel<IdentityLink, false>;
 using HierLogisticRegressionModel = HierGlmModel<LogitLink, false>;
 using HierLinearRegressionCenteredModel = HierGlmModel<IdentityLink, true>;
 using HierLogisticRegressionCenteredModel = HierGlmModel<LogitLink, true>;
+using HierPoissonRegressionModel = HierGlmModel<LogLink, false>;
+using HierPoissonRegressionCenteredModel = HierGlmModel<LogLink, true>;
 
 }  // namespace wn

@@ -252,6 +252,167 @@ WND_HD double dexp(double x) { return dexp(x, array_tables()); }
 WND_HD double dexp_weight(double x) { return dexp_weight(x, array_tables()); }
 WND_HD double dlog(double x) { return dlog(x, array_tables()); }
 
+// ---------------------------------------------------------------------------
+// Count-model maths (models/glm.h LogLink, models/glm_scale.h): log1p, softplus with relative accuracy, and the
+// differences lgamma(y + phi) - lgamma(phi) and psi(y + phi) - psi(phi).  Same rules as dexp / dlog: binary64
+// +,-,*,/, fmad and integer operations only, so the host build of this source gives the device's bits
+// (tests/test_count_math.py against mpmath on the host, tests/test_count_models_gpu.py device against host through
+// wn_internal_count_math_probe).  Accuracy, stated against the absolute version of each computation: DESIGN §3.8.3.
+// ---------------------------------------------------------------------------
+
+// log(1 + x) with relative accuracy as x -> 0: dlog's main path on w = RN(1 + x), with the rounding error e of that
+// sum (two-sum, exact) added to the reduced argument -- 1 + x = 2^k (s + e 2^-k), and s - c is exact, so the only new
+// rounding is that of (s - c) + e 2^-k.  x = -1 -> -inf, x < -1 -> NaN, +inf and NaN -> themselves.
+template <class Tab>
+WND_HD double dlog1p(double x, const Tab& tab) {
+  constexpr double kLn2Hi = 6.93147180369123816490e-01;
+  constexpr double kLn2Lo = 1.90821492927058770002e-10;
+  const double w = 1.0 + x;
+  const double bv = w - 1.0;
+  const double e = (1.0 - (w - bv)) + (x - bv);  // w + e == 1 + x exactly
+  const uint64_t bits = as_u64(w);                // w >= 2^-53 for every x > -1: a normal number
+  int k = static_cast<int>((bits >> 52) & 0x7ff) - 1023;
+  const uint64_t frac = bits & 0x000fffffffffffffULL;
+  const bool upper = frac >= 0x0008000000000000ULL;
+  k += upper ? 1 : 0;
+  const double s = as_f64(frac | (static_cast<uint64_t>(upper ? 1022 : 1023) << 52));
+  const int i = static_cast<int>(fmad(s, 64.0, 0.5));
+  const double c = static_cast<double>(i) * 0.015625;
+  // e 2^-k: |e| <= ulp(w) / 2, so below 2^-1000 relative to s it changes nothing (k is clamped to keep 2^-k normal)
+  const double ek = e * two_to(k < 1000 ? -k : -1000);
+  const double u = ((s - c) + ek) * tab.rcp(i - 48);
+  const double lc = tab.logc(i - 48);
+  const double q = u * u;
+  const double a0 = fmad(-u, 3.33333333333333315e-01, 0.5);
+  const double a1 = fmad(-u, 2.00000000000000011e-01, 0.25);
+  const double a2 = fmad(-u, 1.42857142857142849e-01, 1.66666666666666657e-01);
+  const double q2 = q * q;
+  const double pl = fmad(q2, fmad(q, 0.125, a2), fmad(q, a1, a0));
+  const double l1 = fmad(-q, pl, u);
+  const double dk = static_cast<double>(k);
+  double y = fmad(dk, kLn2Hi, lc) + fmad(dk, kLn2Lo, l1);
+  if (x == __builtin_inf()) y = x;
+  if (x == -1.0) y = -__builtin_inf();
+  if (x < -1.0) y = __builtin_nan("");
+  if (x != x) y = x;
+  return y;
+}
+
+// softplus(t) = log(1 + exp(t)) = max(t, 0) + log1p(exp(-|t|)), relatively accurate for every t (exp(t) itself as
+// t -> -inf: dexp and dlog1p each keep a few ulps there, where log(1 + exp(-|t|)) loses ~u / exp(t)).
+template <class Tab>
+WND_HD double dsoftplus(double t, const Tab& tab) {
+  const double e = dexp(-__builtin_fabs(t), tab);  // (0, 1]
+  return (t > 0.0 ? t : 0.0) + dlog1p(e, tab);
+}
+
+// lgamma(y + phi) - lgamma(phi) and psi(y + phi) - psi(phi) for y >= 0 and phi > 0 (y an integer count in the count
+// models; the schemes hold for any real y >= 0).  No loop over y and no branch on it:
+//   * phi < kGammaShift (16): the shift f(y, phi) = f(y, phi + 16) + log P(phi) - log P(phi + y) and
+//     g(y, phi) = g(y, phi + 16) + P'/P(phi) - P'/P(phi + y), P(z) = z (z + 1) ... (z + 15), P'/P = sum 1 / (z + k);
+//     a fixed 16-step product (and product-rule derivative) per side;
+//   * then, at a = phi or phi + 16 (>= 16) and b = a + y, the asymptotic (Stirling) series of the two differences,
+//       lgamma(b) - lgamma(a) = (a - 1/2) L + y (log a - 1 + L) + S(b) - S(a),    L = log1p(y / a),
+//       psi(b) - psi(a)       = L + y / (2 a b) + U(a) - U(b),
+//     S(z) = 1/(12 z) - 1/(360 z^3) + ... (7 terms, < 2e-18 left at z = 16), U(z) = 1/(12 z^2) - 1/(120 z^4) + ...
+//     (7 terms, < 2e-18 left at z = 16).  Written so, neither difference cancels as phi >> y.
+// Everything that depends on phi alone is GammaConsts, computed once (on the device: once per evaluation, wave-
+// uniform); per argument y the two together take ONE true division (1 / (b P(phi + y)), from which 1 / b and
+// 1 / P(phi + y) follow by one multiplication each), one dlog1p, and one dlog when phi < 16.  y = 0 gives exactly 0.
+constexpr double kGammaShift = 16.0;
+struct GammaConsts {
+  double phi;
+  double a, ia, lam1;  // a = phi (+ 16 when shifted), 1 / a, log(a) - 1
+  double sa, ua;       // S(a), U(a)
+  double pa, ra;       // P(phi) and P'/P(phi) when shifted (1 and 0 otherwise)
+  bool shift;          // phi < 16
+};
+// S(z) for iz = 1 / z
+WND_HD double stirling_s(double iz) {
+  const double w = iz * iz;
+  double p = 6.41025641025641025641e-03;         //  1/156
+  p = fmad(w, p, -1.91752691752691752692e-03);   // -691/360360
+  p = fmad(w, p, 8.41750841750841750842e-04);    //  1/1188
+  p = fmad(w, p, -5.95238095238095238095e-04);   // -1/1680
+  p = fmad(w, p, 7.93650793650793650794e-04);    //  1/1260
+  p = fmad(w, p, -2.77777777777777777778e-03);   // -1/360
+  p = fmad(w, p, 8.33333333333333333333e-02);    //  1/12
+  return iz * p;
+}
+// U(z) = log z - 1/(2 z) - psi(z) for iz = 1 / z
+WND_HD double digamma_u(double iz) {
+  const double w = iz * iz;
+  double p = 8.33333333333333333333e-02;         //  1/12
+  p = fmad(w, p, -2.10927960927960927961e-02);   // -691/32760
+  p = fmad(w, p, 7.57575757575757575758e-03);    //  1/132
+  p = fmad(w, p, -4.16666666666666666667e-03);   // -1/240
+  p = fmad(w, p, 3.96825396825396825397e-03);    //  1/252
+  p = fmad(w, p, -8.33333333333333333333e-03);   // -1/120
+  p = fmad(w, p, 8.33333333333333333333e-02);    //  1/12
+  return w * p;
+}
+// P(z) = prod_{k<16} (z + k) and P'(z), by the product rule, in a fixed order (the same on both sides of the shift)
+WND_HD void shift_product(double z, double& p, double& dp) {
+  p = z;
+  dp = 1.0;
+#pragma unroll
+  for (int k = 1; k < 16; ++k) {
+    const double f = z + static_cast<double>(k);
+    dp = fmad(dp, f, p);
+    p = p * f;
+  }
+}
+template <class Tab>
+WND_HD GammaConsts gamma_consts(double phi, const Tab& tab) {
+  GammaConsts g;
+  g.phi = phi;
+  g.shift = phi < kGammaShift;
+  g.a = g.shift ? phi + kGammaShift : phi;
+  g.ia = 1.0 / g.a;
+  g.lam1 = dlog(g.a, tab) - 1.0;
+  g.sa = stirling_s(g.ia);
+  g.ua = digamma_u(g.ia);
+  double p, dp;
+  shift_product(phi, p, dp);
+  g.pa = g.shift ? p : 1.0;
+  g.ra = g.shift ? dp / p : 0.0;
+  return g;
+}
+// both differences at y; lg = lgamma(y + phi) - lgamma(phi), dg = psi(y + phi) - psi(phi).  `g.shift` is the same
+// for every lane that shares phi, so its branch does not diverge.  Non-finite phi or y, or y so large that
+// b P(phi + y) leaves the normal range (y > ~2^59 with phi < 16), give non-finite results.
+template <class Tab>
+WND_HD void dlgamma_digamma_diff(double y, const GammaConsts& g, const Tab& tab, double& lg, double& dg) {
+  const double b = g.a + y;
+  double py = 1.0, dpy = 0.0;
+  if (g.shift) shift_product(g.phi + y, py, dpy);
+  const double q = 1.0 / (b * py);
+  const double ib = py * q;
+  const double L = dlog1p(y * g.ia, tab);
+  double l = (g.a - 0.5) * L + y * (g.lam1 + L) + (stirling_s(ib) - g.sa);
+  double d = (L + 0.5 * y * g.ia * ib) + (g.ua - digamma_u(ib));
+  if (g.shift) {
+    const double ipy = b * q;
+    l = l + dlog(g.pa * ipy, tab);
+    d = d + (g.ra - dpy * ipy);
+  }
+  const bool lost = !(q >= 2.2250738585072014e-308);  // 1 / (b P) subnormal, zero or NaN
+  lg = y == 0.0 ? 0.0 : (lost ? __builtin_nan("") : l);
+  dg = y == 0.0 ? 0.0 : (lost ? __builtin_nan("") : d);
+}
+template <class Tab>
+WND_HD double dlgamma_diff(double y, double phi, const Tab& tab) {
+  double lg, dg;
+  dlgamma_digamma_diff(y, gamma_consts(phi, tab), tab, lg, dg);
+  return lg;
+}
+template <class Tab>
+WND_HD double ddigamma_diff(double y, double phi, const Tab& tab) {
+  double lg, dg;
+  dlgamma_digamma_diff(y, gamma_consts(phi, tab), tab, lg, dg);
+  return dg;
+}
+
 // x^y for x > 0; the path's only use is Adam's t^decay (adam.hpp:83)
 template <class Tab>
 WND_HD double dpow_pos(double x, double y, const Tab& tab) {

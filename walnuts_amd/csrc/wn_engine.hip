@@ -44,6 +44,23 @@ static __global__ void sqrt_probe_kernel(const double* x, double* y, long long n
     y[i] = checked ? wnd::sqrt_normal<true>(x[i]) : wnd::sqrt_normal<false>(x[i]);
 }
 
+// (internal, for the tests) the count models' maths on the device (wnd::dlog1p, dsoftplus, dlgamma_diff, ddigamma_diff)
+static __global__ void count_math_probe_kernel(const double* x, const double* phi, double* y, long long n, int fn) {
+  const wnd::ArrayTables tab = wnd::array_tables();
+  for (long long i = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; i < n;
+       i += static_cast<long long>(gridDim.x) * blockDim.x) {
+    if (fn == 0) {
+      y[i] = wnd::dlog1p(x[i], tab);
+    } else if (fn == 1) {
+      y[i] = wnd::dsoftplus(x[i], tab);
+    } else if (fn == 2) {
+      y[i] = wnd::dlgamma_diff(x[i], phi[i], tab);
+    } else {
+      y[i] = wnd::ddigamma_diff(x[i], phi[i], tab);
+    }
+  }
+}
+
 struct wn_engine {
   int model = 0, D = 0, Dp = 0;
   size_t C = 0;
@@ -463,7 +480,8 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   ops.validate(num_params);
   if (ops.uses_data && data == nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model is conditioned on data: create it with "
-                                "wn_engine_create_with_data (x [num_obs][num_params], y [num_obs])");
+                                "wn_engine_create_with_data (x [num_obs][" +
+                                std::string(ops.scale_param ? "num_params - 1" : "num_params") + "], y [num_obs])");
   if (!ops.uses_data && data != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
   if (ops.uses_groups && data != nullptr && data->group == nullptr)
@@ -472,8 +490,9 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
                                 "[num_obs] in [0, num_groups))");
   if (!ops.uses_groups && data != nullptr && data->group != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
-  // columns of x: num_params, or P = num_params - J - 1 for a grouped model
-  int cols = num_params;
+  // columns of x: num_params, num_params - 1 for a model with a scale parameter, or P = num_params - J - 1 for a
+  // grouped model
+  int cols = ops.scale_param ? num_params - 1 : num_params;
   if (ops.uses_groups && data != nullptr) {
     const int J = data->num_groups;
     if (J < 1 || num_params - J - 1 < 1)
@@ -798,6 +817,33 @@ int wn_internal_sqrt_probe(const double* x, double* y, size_t n, int checked) {
     return -1;
   }
   return 0;
+}
+
+int wn_internal_count_math_probe(const double* x, const double* phi, double* y, size_t n, int fn) {
+  DevBuf<double> dx, dp, dy;
+  try {
+    dx.alloc(n);
+    dp.alloc(n);
+    dy.alloc(n);
+    HIP_OK(hipMemcpyAsync(dx.p, x, n * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    HIP_OK(hipMemcpyAsync(dp.p, phi, n * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(count_math_probe_kernel, dim3(1024), dim3(256), 0, nullptr, dx.p, dp.p, dy.p,
+                       static_cast<long long>(n), fn);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(y, dy.p, n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIP_OK(hipStreamSynchronize(nullptr));
+  } catch (...) {
+    return -1;
+  }
+  return 0;
+}
+
+int wn_model_data_columns(int model, int num_params, int num_groups) {
+  if (model < 0 || model >= wn::kMaxModels) return -1;
+  const wn::ModelOps* ops = wn::model_table()[model];
+  if (ops == nullptr || !ops->uses_data) return -1;
+  if (ops->uses_groups) return num_groups >= 1 ? num_params - num_groups - 1 : -1;
+  return ops->scale_param ? num_params - 1 : num_params;
 }
 
 int wn_model_id(const char* name) {

@@ -21,6 +21,9 @@ static constexpr bool kHasStreaming = WN_MODEL_TYPE::kElementwise || is_streamab
 static constexpr bool kUsesData = uses_data<WN_MODEL_TYPE>::value;
 static_assert(!(kUsesData && kHasStreaming), "a data model has no streaming form (wn_model_api.h)");
 static_assert(!uses_groups<WN_MODEL_TYPE>::value || kUsesData, "kUsesGroups needs kUsesData (wn_model_api.h)");
+static_assert(!scale_param<WN_MODEL_TYPE>::value || kUsesData, "kScaleParam needs kUsesData (wn_model_api.h)");
+static_assert(!(scale_param<WN_MODEL_TYPE>::value && uses_groups<WN_MODEL_TYPE>::value),
+              "kScaleParam and kUsesGroups do not combine (wn_model_api.h)");
 static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }
 
 void WN_CAT(launch_transition_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem, hipStream_t stream,
@@ -245,7 +248,8 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     kUsesData,
     &WN_CAT(launch_eval_, WN_MODEL_TAG),
     &WN_CAT(host_data_, WN_MODEL_TAG),
-    uses_groups<WN_MODEL_TYPE>::value};
+    uses_groups<WN_MODEL_TYPE>::value,
+    scale_param<WN_MODEL_TYPE>::value};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

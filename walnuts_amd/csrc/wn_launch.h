@@ -188,6 +188,7 @@ struct ModelOps {
   // data models: validate the observations before upload (x [num_obs][num_params] row-major, y [num_obs])
   void (*host_data)(const double* x, const double* y, int num_obs, int num_params);
   bool uses_groups;  // a data model that reads a group index per observation (kUsesGroups)
+  bool scale_param;  // a flat data model whose last coordinate is a scale parameter, not a column of x (kScaleParam)
 };
 constexpr int kMaxModels = 64;
 inline const ModelOps** model_table() {
@@ -202,7 +203,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 11;
+constexpr int kModelAbiVersion = 12;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

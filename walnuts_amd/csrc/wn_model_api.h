@@ -66,6 +66,10 @@
 //     // columns, stored at the narrower row stride Dx = 128 * ceil(P / 128) (host_data's last argument is P).
 //     // wn_engine_create refuses a grouped model without groups and groups for a model without this member.
 //     static constexpr bool kUsesGroups = true;
+//     // ... or, on top of kUsesData and NOT with kUsesGroups (a static_assert), a SCALE PARAMETER as the last
+//     // coordinate: x has P = num_params - 1 columns, stored at the flat stride Dp with column num_params - 1 zero, so
+//     // the row pass never sees the scale (host_data's last argument is P).  models/glm_scale.h.
+//     static constexpr bool kScaleParam = true;
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -100,15 +104,18 @@
 //
 // Registration is a five-line translation unit, wn_kernels_<name>.hip, that the Makefile picks up by its name:
 //   #include "models/my_model.h"
-//   #define WN_MODEL_ID 6                 // 0-5 and 15-18 are taken (std_normal, diag_normal, funnel, rw1,
+//   #define WN_MODEL_ID 6                 // 0-5, 15-18 and 24-28 are taken (std_normal, diag_normal, funnel, rw1,
 //                                         //   linear_regression, logistic_regression; hier_linear_regression,
-//                                         //   hier_logistic_regression and their _centered forms); < 64
+//                                         //   hier_logistic_regression and their _centered forms; poisson_regression,
+//                                         //   neg_binomial_regression, linear_regression_sigma,
+//                                         //   hier_poisson_regression and its _centered form); < 64
 //   #define WN_MODEL_TAG my_model         // wn_model_id("my_model") finds it at run time
 //   #define WN_MODEL_TYPE wn::MyModel
 //   #include "wn_kernels.inc"
 // models/rw1.h is a complete example (the reference's AR(1) density with a neighbour-coupled gradient); models/glm.h
-// one of a model conditioned on data (Bayesian linear and logistic regression); models/hier_glm.h one with a group
-// channel (hierarchical regression with varying intercepts).
+// one of a model conditioned on data (Bayesian linear, logistic and Poisson regression); models/hier_glm.h one with a
+// group channel (hierarchical regression with varying intercepts); models/glm_scale.h one with a scale parameter
+// (negative binomial regression, linear regression with an estimated noise level).
 #pragma once
 
 #include "wn_devmath.h"

@@ -973,6 +973,12 @@ template <class M, class = void>
 struct uses_groups : std::false_type {};
 template <class M>
 struct uses_groups<M, std::enable_if_t<M::kUsesGroups>> : std::true_type {};
+// ... and a flat data model whose last coordinate is a scale parameter, not a column of x (kScaleParam: x has
+// num_params - 1 columns, stored at the flat stride Dp with column num_params - 1 zero)
+template <class M, class = void>
+struct scale_param : std::false_type {};
+template <class M>
+struct scale_param<M, std::enable_if_t<M::kScaleParam>> : std::true_type {};
 template <class M, bool Elementwise = M::kElementwise>
 struct StreamTraits {
   static constexpr bool kTwoPass = false, kHasSums = false, kHalo = false;

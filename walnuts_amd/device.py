@@ -158,12 +158,17 @@ def walnuts_device(
     block -- the call returns ``(results, [chains on devices[0], chains on devices[1], ...])``.
 
     ``data=(x, y)`` (walnutpie_sample_device_data / _data_resident): the observations of a model conditioned on data
-    (``MODEL_LINEAR_REGRESSION``, ``MODEL_LOGISTIC_REGRESSION`` or a model of your own that declares ``kUsesData``),
-    ``x`` of shape (num_obs, num_params) and ``y`` of shape (num_obs,); copied to the device once.  One device only:
+    (``MODEL_LINEAR_REGRESSION``, ``MODEL_LOGISTIC_REGRESSION``, the count models below or a model of your own that
+    declares ``kUsesData``), ``x`` of shape (num_obs, num_params) and ``y`` of shape (num_obs,); copied to the device once.  One device only:
     not with ``devices`` or ``reference_streams``.
 
     ``data=(x, y, group)`` (walnutpie_sample_device_grouped / _grouped_resident): a grouped model (MODEL_HIER_*), x of
     shape (num_obs, P), groups in [0, J), J = num_params - P - 1; ``datasets=`` then takes triples (x, y, group).
+
+    Count models and an estimated noise level: ``MODEL_POISSON_REGRESSION`` takes data as the linear and logistic
+    models; ``MODEL_NEG_BINOMIAL_REGRESSION`` and ``MODEL_LINEAR_REGRESSION_SIGMA`` end theta with the log scale s, so
+    their x has num_params - 1 columns and ``model_params`` is [prior variances of beta | sigma_0];
+    ``MODEL_HIER_POISSON_REGRESSION`` and ``_CENTERED`` take (x, y, group) as the other MODEL_HIER_* models.
 
     ``datasets=[(x0, y0), (x1, y1), ...]`` (walnutpie_sample_device_datasets / _datasets_resident): G datasets of the
     same model and prior, fitted in one run.  ``num_chains`` (the total) must be a multiple k of G; chains
@@ -216,15 +221,15 @@ def walnuts_device(
         grouped = True
         data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), grp.ctypes.data_as(_ffi._i32p), J, y.size)
     elif data is not None:
-        from .engine import _data_arrays
+        from .engine import _data_arrays, _data_columns
 
-        x, y = _data_arrays(data, num_params)
+        x, y = _data_arrays(data, _data_columns(lib, model, num_params))
         data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), y.size)
     num_datasets = 1
     if datasets is not None:
-        from .engine import _datasets_arrays
+        from .engine import _data_columns, _datasets_arrays
 
-        x, y, offsets, grp, J = _datasets_arrays(datasets, num_params)
+        x, y, offsets, grp, J = _datasets_arrays(datasets, num_params, _data_columns(lib, model, num_params))
         num_datasets = offsets.size - 1
         grouped = grp is not None
         data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp)) + (

@@ -23,6 +23,13 @@ MODEL_LINEAR_REGRESSION, MODEL_LOGISTIC_REGRESSION = 4, 5
 # (ids 6-14 stay free for models of one's own: the out-of-tree examples and tests take ids there)
 MODEL_HIER_LINEAR_REGRESSION, MODEL_HIER_LOGISTIC_REGRESSION = 15, 16
 MODEL_HIER_LINEAR_REGRESSION_CENTERED, MODEL_HIER_LOGISTIC_REGRESSION_CENTERED = 17, 18
+# count models and an estimated noise level (walnuts_amd/csrc/models/glm.h, glm_scale.h), ids 24-28 (19-23 stay free as
+# well).  poisson_regression: as the linear and logistic models.  neg_binomial_regression (NB2, overdispersion
+# kappa = exp(s)) and linear_regression_sigma (noise sigma = exp(s)): theta = [beta (P) | s], params = [prior variances
+# of beta (P) | sigma_0, the half-normal scale of exp(s)], data = (x, y) with x of P = num_params - 1 columns.
+# hier_poisson_regression(_centered): as MODEL_HIER_*, with Poisson counts.
+MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA = 24, 25, 26
+MODEL_HIER_POISSON_REGRESSION, MODEL_HIER_POISSON_REGRESSION_CENTERED = 27, 28
 _dp = _ffi._dp
 
 
@@ -53,8 +60,17 @@ def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _data_columns(lib, model: int, num_params: int) -> int:
+    """Columns of x that the library's data model `model` reads at num_params (wn_model_data_columns): num_params, or
+    num_params - 1 for a model with a scale parameter.  An id that holds no flat data model gives num_params, and the
+    engine then refuses the model (or the pair (x, y) for a grouped model) with its own message."""
+    cols = int(lib.wn_model_data_columns(int(model), int(num_params), 0))
+    return cols if cols >= 0 else int(num_params)
+
+
 def _data_arrays(data, num_params: int):
-    """(x, y) of a data model as contiguous float64 arrays: x (num_obs, num_params), y (num_obs,)."""
+    """(x, y) of a data model as contiguous float64 arrays: x (num_obs, num_params), y (num_obs,).  `num_params` is the
+    width x must have: _data_columns() of the model."""
     try:
         x, y = data
     except (TypeError, ValueError):
@@ -98,7 +114,7 @@ def _is_grouped(data) -> bool:
         return False
 
 
-def _datasets_arrays(datasets, num_params: int):
+def _datasets_arrays(datasets, num_params: int, cols: Optional[int] = None):
     """Several datasets [(x0, y0), (x1, y1), ...] as one block: x (rows, num_params) and y (rows,) stacked in order,
     and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1]).  Triples (x, y, group) of a grouped
     model give x (rows, P) and a fourth and fifth entry: the stacked int32 groups and J; pairs give None, 0 there."""
@@ -117,7 +133,7 @@ def _datasets_arrays(datasets, num_params: int):
             raise ValueError("every dataset's x must have the same number of columns")
     else:
         try:
-            parts = [_data_arrays(d, num_params) for d in items]
+            parts = [_data_arrays(d, num_params if cols is None else cols) for d in items]
         except TypeError:
             raise ValueError("datasets must be a sequence of (x, y) pairs") from None
     offsets = np.zeros(len(parts) + 1, dtype=np.int64)
@@ -135,7 +151,10 @@ class DeviceEngine:
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
         (num_obs, dim) and y of shape (num_obs,); copied to the device once.  `data=(x, y, group)` for a grouped model
         (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
-        [0, J) with J = dim - P - 1 (wn_engine_create_with_grouped_data).
+        [0, J) with J = dim - P - 1 (wn_engine_create_with_grouped_data).  A model with a scale parameter
+        (MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA) takes x of shape (num_obs, dim - 1): its last
+        coordinate is s, not a column of x.  The count models (MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION,
+        MODEL_HIER_POISSON_REGRESSION*) need every y to be a finite non-negative integer.
 
         `datasets=[(x0, y0), (x1, y1), ...]` instead: G datasets of the same model and prior (sizes may differ), fitted
         side by side (wn_engine_create_with_datasets).  num_chains must be a multiple k of G; chains [g*k, (g+1)*k)
@@ -155,7 +174,7 @@ class DeviceEngine:
         pp = None if p is None else p.ctypes.data_as(_dp)
         self._several = datasets is not None
         if datasets is not None:
-            x, y, off, grp, J = _datasets_arrays(datasets, self.D)
+            x, y, off, grp, J = _datasets_arrays(datasets, self.D, _data_columns(self.lib, model, self.D))
             if grp is not None:
                 rc = self.lib.wn_engine_create_with_grouped_datasets(
                     C.byref(h), model, dim, pp, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp),
@@ -173,7 +192,7 @@ class DeviceEngine:
                                                              y.ctypes.data_as(_dp), grp.ctypes.data_as(_ffi._i32p), J,
                                                              y.size, num_chains, C.byref(self.cfg), C.byref(err))
         else:
-            x, y = _data_arrays(data, self.D)
+            x, y = _data_arrays(data, _data_columns(self.lib, model, self.D))
             rc = self.lib.wn_engine_create_with_data(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
                                                      y.ctypes.data_as(_dp), y.size, num_chains, C.byref(self.cfg),
                                                      C.byref(err))
