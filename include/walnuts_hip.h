@@ -146,128 +146,58 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
     int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
     int thin, wn_chains** chains_out, WalnutpyError** err);
 
-/* walnutpie_sample_device / _resident for a model conditioned on data (walnuts_amd/csrc/wn_model_api.h, kUsesData:
- * MODEL_LINEAR_REGRESSION, MODEL_LOGISTIC_REGRESSION, or a model of your own): x [num_obs][num_params] row-major and
- * y [num_obs], host pointers, checked and copied to the device once (not retained).  Everything else as the calls
- * above.  One device only: the multi-device and reference-stream entry points take no data.
- * Count models and an estimated noise level (walnuts_amd/csrc/models/glm.h, glm_scale.h) use the same calls:
- * poisson_regression (24) as linear_regression; neg_binomial_regression (25, NB2: kappa = exp(s), Var y = mu + kappa
- * mu^2) and linear_regression_sigma (26, noise sigma = exp(s)) end theta with the log scale s, so their x has
- * num_params - 1 columns and model_params is [prior variances (num_params - 1) | sigma_0], the half-normal scale of
- * exp(s).  The count models refuse a y that is not a finite non-negative integer (`config`).  hier_poisson_regression
- * (27) and its _centered form (28) take the grouped calls below. */
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_data(
-    int model, const double* model_params, int num_params, const double* x, const double* y, int num_obs,
-    const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    WalnutpyError** err);
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_data_resident(
-    int model, const double* model_params, int num_params, const double* x, const double* y, int num_obs,
-    const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    int thin, wn_chains** chains_out, WalnutpyError** err);
+/* The observations of a model conditioned on data (walnuts_amd/csrc/wn_model_api.h, kUsesData: linear_regression,
+ * logistic_regression, ..., or a model of your own): host pointers, checked and copied to the device once (not retained).
+ * cols = wn_model_data_columns(model, num_params, num_groups): num_params for the flat models; num_params - 1 for
+ * neg_binomial_regression (25, NB2: kappa = exp(s), Var y = mu + kappa mu^2) and linear_regression_sigma (26, noise
+ * sigma = exp(s)), which end theta with the log scale s and take model_params [prior variances (num_params - 1) |
+ * sigma_0], the half-normal scale of exp(s); P = num_params - num_groups - 1 (P >= 1, num_groups >= 1) for a GROUPED
+ * model (kUsesGroups: the hier_* models and their _centered forms, walnuts_amd/csrc/models/hier_glm.h), which also reads
+ * `group`.  The count models refuse a y that is not a finite non-negative integer (`config`).
+ * MANY datasets at once (one model, one prior): with obs_offsets != NULL, dataset g is rows [obs_offsets[g],
+ * obs_offsets[g + 1]) of x, y and group (from 0, strictly increasing; datasets may differ in size; num_groups is shared
+ * and a dataset may leave groups empty), and chain c is conditioned on dataset c / k, k = num_chains / num_datasets
+ * (num_chains a multiple of num_datasets). */
+typedef struct wn_observations {
+  const double* x;            /* [rows][cols] row-major */
+  const double* y;            /* [rows] */
+  int num_obs;                /* rows of the one shared block; ignored when obs_offsets != NULL */
+  const int32_t* group;       /* [rows], each in [0, num_groups); NULL for a model without groups */
+  int num_groups;
+  const int64_t* obs_offsets; /* [num_datasets + 1]; NULL: one block shared by every chain */
+  int num_datasets;
+} wn_observations;
 
-/* walnutpie_sample_device_data / _data_resident over MANY datasets at once (one model, one prior): dataset g is rows
- * [obs_offsets[g], obs_offsets[g + 1]) of x and y (obs_offsets[num_datasets + 1], int64, from 0, strictly increasing;
- * datasets may differ in size), and num_chains (the total) = num_datasets * k: chains [g * k, (g + 1) * k) are
- * conditioned on dataset g.  Random streams stay keyed by the global chain id (the transition key is seed + id +
- * num_chains), so dataset g's block of out / final_lengths / stepsize_out / inv_metric_out / the resident block is, bit
- * for bit, what walnutpie_sample_device_data on dataset g alone would write for the same chain ids.  The stopping rules
- * are per dataset, in lock step: warmup ends at the first look where EVERY dataset's spread meets both tolerances,
- * sampling at the first R-hat look (only when k > 1) where every dataset's R-hat is at most rhat_converge_tol; the
- * progress line prints the largest R-hat.  Outputs keep the layout of the calls above.  One device only. */
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_datasets(
-    int model, const double* model_params, int num_params, const double* x, const double* y, const int64_t* obs_offsets,
-    int num_datasets, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    WalnutpyError** err);
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_datasets_resident(
-    int model, const double* model_params, int num_params, const double* x, const double* y, const int64_t* obs_offsets,
-    int num_datasets, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    int thin, wn_chains** chains_out, WalnutpyError** err);
-/* The same four calls for a GROUPED model (kUsesGroups: hier_linear_regression, hier_logistic_regression,
- * hier_poisson_regression and their
- * _centered forms, walnuts_amd/csrc/models/hier_glm.h): group [rows] (int32, every entry in [0, num_groups)) and
- * num_groups after y; x then has P = num_params - num_groups - 1 columns (P >= 1, num_groups >= 1).  With several
- * datasets the groups are sliced by obs_offsets like x and y, and num_groups is shared (a dataset may leave groups
- * empty).  Refusals as for wn_engine_create_with_grouped_data. */
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped(
-    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
-    int num_groups, int num_obs, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    WalnutpyError** err);
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped_resident(
-    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
-    int num_groups, int num_obs, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    int thin, wn_chains** chains_out, WalnutpyError** err);
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped_datasets(
-    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
-    int num_groups, const int64_t* obs_offsets, int num_datasets, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    WalnutpyError** err);
-WALNUTS_HIP_EXPORT int walnutpie_sample_device_grouped_datasets_resident(
-    int model, const double* model_params, int num_params, const double* x, const double* y, const int32_t* group,
-    int num_groups, const int64_t* obs_offsets, int num_datasets, const double* inits, size_t num_chains,
-    unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric, int min_warmup_iter,
-    int max_warmup_iter, int min_sampling_iter, int max_sampling_iter, int max_trajectory_doublings,
-    int max_step_halvings, int min_micro_steps, double max_hamiltonian_error, double step_size_converge_tol,
-    double mass_converge_tol, double rhat_converge_tol, double mass_init_count, double mass_additive_smoothing,
-    double max_macro_steps_target, double step_size_init, double step_accept_rate_target,
-    double step_learning_rate, double step_gradient_decay, double step_sq_gradient_decay,
-    double step_stabilization, double step_learn_rate_decay, bool save_warmup, double* out, size_t out_size,
-    int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh, PRINT_CALLBACK print,
-    int thin, wn_chains** chains_out, WalnutpyError** err);
+/* walnutpie_sample_device / _resident for a model conditioned on data: `obs` after num_params, everything else as the
+ * calls above.  One device only: the multi-device and reference-stream entry points take no data.  With several
+ * datasets the random streams stay keyed by the global chain id (the transition key is seed + id + num_chains), so
+ * dataset g's block of out / final_lengths / stepsize_out / inv_metric_out / the resident block is, bit for bit, what
+ * the call on dataset g alone would write for the same chain ids.  The stopping rules are per dataset, in lock step:
+ * warmup ends at the first look where EVERY dataset's spread meets both tolerances, sampling at the first R-hat look
+ * (only when k > 1) where every dataset's R-hat is at most rhat_converge_tol; the progress line prints the largest
+ * R-hat.  Refusals as for wn_engine_create_observed. */
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_observed(
+    int model, const double* model_params, int num_params, const wn_observations* obs, const double* inits,
+    size_t num_chains, unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric,
+    int min_warmup_iter, int max_warmup_iter, int min_sampling_iter, int max_sampling_iter,
+    int max_trajectory_doublings, int max_step_halvings, int min_micro_steps, double max_hamiltonian_error,
+    double step_size_converge_tol, double mass_converge_tol, double rhat_converge_tol, double mass_init_count,
+    double mass_additive_smoothing, double max_macro_steps_target, double step_size_init,
+    double step_accept_rate_target, double step_learning_rate, double step_gradient_decay,
+    double step_sq_gradient_decay, double step_stabilization, double step_learn_rate_decay, bool save_warmup,
+    double* out, size_t out_size, int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh,
+    PRINT_CALLBACK print, WalnutpyError** err);
+WALNUTS_HIP_EXPORT int walnutpie_sample_device_observed_resident(
+    int model, const double* model_params, int num_params, const wn_observations* obs, const double* inits,
+    size_t num_chains, unsigned int seed, unsigned int id, double init_radius, const double* init_inv_metric,
+    int min_warmup_iter, int max_warmup_iter, int min_sampling_iter, int max_sampling_iter,
+    int max_trajectory_doublings, int max_step_halvings, int min_micro_steps, double max_hamiltonian_error,
+    double step_size_converge_tol, double mass_converge_tol, double rhat_converge_tol, double mass_init_count,
+    double mass_additive_smoothing, double max_macro_steps_target, double step_size_init,
+    double step_accept_rate_target, double step_learning_rate, double step_gradient_decay,
+    double step_sq_gradient_decay, double step_stabilization, double step_learn_rate_decay, bool save_warmup,
+    double* out, size_t out_size, int* final_lengths, double* stepsize_out, double* inv_metric_out, int refresh,
+    PRINT_CALLBACK print, int thin, wn_chains** chains_out, WalnutpyError** err);
 
 /* walnutpie_sample_device over SEVERAL devices of the node ("one process, one driver thread +
  * stream per GPU").  devices[num_devices]: HIP ordinals; shard s -- a contiguous block of the global chain ids, sizes
@@ -421,46 +351,21 @@ WALNUTS_HIP_EXPORT int wn_geometry_candidates(int num_params, int waves_per_chai
 /* model_params: host pointer (copied). */
 WALNUTS_HIP_EXPORT int wn_engine_create(wn_engine** out, int model, int num_params, const double* model_params,
                                         size_t num_chains, const wn_config* cfg, WalnutpyError** err);
-/* A model conditioned on data (kUsesData): the observations x [num_obs][num_params] row-major and y [num_obs] (host
- * pointers, checked -- finite; the model's own checks, e.g. y in {0, 1} for logistic_regression -- and copied to the
- * device in the layout of a theta row; not retained; freed by wn_engine_destroy).  A data model created through
- * wn_engine_create, data for a model without kUsesData, and a data model outside one wavefront per chain
- * (num_params > 1024, or an explicit wider geometry) are `config` errors. */
-WALNUTS_HIP_EXPORT int wn_engine_create_with_data(wn_engine** out, int model, int num_params, const double* model_params,
-                                                  const double* x, const double* y, int num_obs, size_t num_chains,
-                                                  const wn_config* cfg, WalnutpyError** err);
-/* MANY datasets of one data model in one engine (one prior, model_params shared): dataset g is rows
- * [obs_offsets[g], obs_offsets[g + 1]) of x [rows][num_params] and y [rows] (obs_offsets[num_datasets + 1], int64,
- * starting at 0, strictly increasing: sizes may differ), and chain c is conditioned on dataset c / k, k = num_chains /
- * num_datasets (num_chains a multiple of num_datasets).  Random streams stay keyed by the chain id, so chain c of
- * dataset g evolves bit for bit as chain c - g * k of an engine created with wn_engine_create_with_data on dataset g
- * alone and seeded with chain_offset = g * k.  Config errors: num_datasets < 1, num_chains not a multiple of it,
- * offsets not from 0 or not strictly increasing, non-finite data, a model without kUsesData, the model's own data
- * checks failing for a dataset (the message names it), and the geometry rules of wn_engine_create_with_data.
- * The pooled statistics below keep their meaning (all chains); the _datasets ones are per dataset. */
-WALNUTS_HIP_EXPORT int wn_engine_create_with_datasets(wn_engine** out, int model, int num_params,
-                                                      const double* model_params, const double* x, const double* y,
-                                                      const int64_t* obs_offsets, int num_datasets, size_t num_chains,
-                                                      const wn_config* cfg, WalnutpyError** err);
-/* A GROUPED data model (kUsesGroups; walnuts_amd/csrc/models/hier_glm.h): as wn_engine_create_with_data, plus the
- * group of every observation, group [num_obs] (int32, host pointer, copied) with values in [0, num_groups).  x has
- * P = num_params - num_groups - 1 columns (x [num_obs][P] row-major), stored on the device at the row stride
- * 128 * ceil(P / 128).  Config errors, beside those of wn_engine_create_with_data: num_params != P + num_groups + 1
- * with P >= 1 and num_groups >= 1, a group outside [0, num_groups), a grouped model created without groups (through
- * wn_engine_create_with_data or _datasets), and groups for a model without kUsesGroups. */
-WALNUTS_HIP_EXPORT int wn_engine_create_with_grouped_data(wn_engine** out, int model, int num_params,
-                                                          const double* model_params, const double* x, const double* y,
-                                                          const int32_t* group, int num_groups, int num_obs,
-                                                          size_t num_chains, const wn_config* cfg, WalnutpyError** err);
-/* ... and several datasets of it (wn_engine_create_with_datasets): group [obs_offsets[num_datasets]] is sliced by
- * obs_offsets like x and y; num_groups is shared by every dataset. */
-WALNUTS_HIP_EXPORT int wn_engine_create_with_grouped_datasets(wn_engine** out, int model, int num_params,
-                                                              const double* model_params, const double* x,
-                                                              const double* y, const int32_t* group, int num_groups,
-                                                              const int64_t* obs_offsets, int num_datasets,
-                                                              size_t num_chains, const wn_config* cfg,
-                                                              WalnutpyError** err);
-/* datasets of an engine (1 for one created without wn_engine_create_with_datasets) */
+/* A model conditioned on data (kUsesData): *obs (wn_observations above; host pointers, checked -- finite; the model's
+ * own checks, e.g. y in {0, 1} for logistic_regression -- and copied to the device, x in the layout of a theta row -- a
+ * grouped model's at the row stride 128 * ceil(P / 128); not retained; freed by wn_engine_destroy).  With several
+ * datasets chain c of dataset g evolves bit for bit as chain c - g * k of an engine created on dataset g alone and
+ * seeded with chain_offset = g * k; the pooled statistics below keep their meaning (all chains), the _datasets ones are
+ * per dataset.  `config` errors: obs == NULL; a data model created through wn_engine_create; data for a model without
+ * kUsesData; a grouped model without `group`, and `group` for a model without kUsesGroups; num_params != P + num_groups
+ * + 1 with P >= 1 and num_groups >= 1; num_datasets < 1, num_chains not a multiple of it, offsets not from 0 or not
+ * strictly increasing; non-finite data; a group outside [0, num_groups); the model's own data checks failing (for a
+ * dataset: the message names it); a data model outside one wavefront per chain (num_params > 1024, or an explicit wider
+ * geometry). */
+WALNUTS_HIP_EXPORT int wn_engine_create_observed(wn_engine** out, int model, int num_params, const double* model_params,
+                                                 const wn_observations* obs, size_t num_chains, const wn_config* cfg,
+                                                 WalnutpyError** err);
+/* datasets of an engine (1 for one created without obs_offsets) */
 WALNUTS_HIP_EXPORT int wn_engine_num_datasets(const wn_engine* e);
 WALNUTS_HIP_EXPORT void wn_engine_destroy(wn_engine* e);
 /* The engine's model at positions the caller chooses: theta [C*D] in, logp_out [C] and grad_out [C*D] out (host
@@ -564,7 +469,7 @@ WALNUTS_HIP_EXPORT int wn_engine_lp_sums(wn_engine* e, double* out3, WalnutpyErr
 WALNUTS_HIP_EXPORT int wn_engine_lp_sq_dev(wn_engine* e, double mean_of_means, double* out1, WalnutpyError** err);
 WALNUTS_HIP_EXPORT int wn_engine_warmup_spread(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
                                                WalnutpyError** err);
-/* The same monitors per dataset of an engine from wn_engine_create_with_datasets (a config error on others): out
+/* The same monitors per dataset of an engine created with obs_offsets (a config error on others): out
  * arrays of num_datasets entries; entry g equals, bit for bit, what wn_engine_rhat / wn_engine_warmup_spread return on
  * a standalone engine of dataset g's k chains in the same state.  wn_engine_average_masses_datasets: every chain's
  * masses become the geometric mean over the chains of ITS dataset (wn_engine_average_masses keeps averaging over all

@@ -1,5 +1,5 @@
 """Probe (not a test): gradient-evaluation rate of logistic regression with many datasets in one engine
-(wn_engine_create_with_datasets) against one shared block, on one GPU.
+(wn_observations::obs_offsets) against one shared block, on one GPU.
 
   python tests/gpu_probes/datasets_rate.py [--chains 16384] [--dim 100] [--obs 1000] [--datasets 0 16 256 4096]
 

@@ -203,7 +203,7 @@ def test_refusals(sim):
 
 @pytest.mark.timeout(900)
 def test_drop_in_call_with_data(sim):
-    """walnutpie_sample_device_data and _data_resident under the emulation: same draws."""
+    """walnutpie_sample_device_observed and _observed_resident under the emulation: same draws."""
     x, y, s2 = make_data(LOG, 5, 40, seed=2)
     kw = dict(model_params=s2, num_params=5, num_chains=3, seed=9, min_warmup_iter=6, max_warmup_iter=6,
               min_sampling_iter=5, max_sampling_iter=5, lib_path=sim, data=(x, y))

@@ -1,5 +1,5 @@
-"""CPU tier: many datasets of one data model in one engine (wn_engine_create_with_datasets, DeviceEngine(datasets=...),
-walnutpie_sample_device_datasets*, walnuts_device(datasets=...)) under the workgroup emulation.
+"""CPU tier: many datasets of one data model in one engine (wn_engine_create_observed with obs_offsets,
+DeviceEngine(datasets=...), walnutpie_sample_device_observed*, walnuts_device(datasets=...)) under the workgroup emulation.
 
 The contract checked here: chain c of dataset g = c // k evolves bit for bit as chain c - g*k of a standalone engine
 built from dataset g alone and seeded with chain_offset = g*k; the per-dataset statistics equal the standalone engines'
@@ -337,9 +337,10 @@ def test_refusals(sim):
         h, err = C.c_void_p(), C.c_void_p()
         xs, ys = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(ys, dtype=np.float64)
         off = np.ascontiguousarray(offsets, dtype=np.int64)
-        rc = lib.wn_engine_create_with_datasets(C.byref(h), model, D, None if params is None else params.ctypes.data_as(wa._ffi._dp),
-                                                xs.ctypes.data_as(wa._ffi._dp), ys.ctypes.data_as(wa._ffi._dp),
-                                                off.ctypes.data_as(wa._ffi._i64p), G, chains, C.byref(cfg), C.byref(err))
+        obs = wa._ffi.Observations(x=xs.ctypes.data_as(wa._ffi._dp), y=ys.ctypes.data_as(wa._ffi._dp),
+                                   obs_offsets=off.ctypes.data_as(wa._ffi._i64p), num_datasets=G)
+        rc = lib.wn_engine_create_observed(C.byref(h), model, D, None if params is None else params.ctypes.data_as(wa._ffi._dp),
+                                           C.byref(obs), chains, C.byref(cfg), C.byref(err))
         if rc == 0:
             lib.wn_engine_destroy(h)
             return None

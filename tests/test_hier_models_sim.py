@@ -369,8 +369,8 @@ def test_refusals(sim):
 
 @pytest.mark.timeout(1200)
 def test_drop_in_calls(sim):
-    """walnutpie_sample_device_grouped* and _grouped_datasets* under the emulation: host and resident draws agree, and
-    dataset g of the datasets call equals a grouped call on dataset g alone."""
+    """walnutpie_sample_device_observed* with groups, one block and several, under the emulation: host and resident
+    draws agree, and dataset g of the datasets call equals a grouped call on dataset g alone."""
     x, y, group, mp = make_hier(HLOG, 3, 4, 25, seed=2)
     D = 8
     kw = dict(model_params=mp, num_params=D, num_chains=2, seed=9, min_warmup_iter=5, max_warmup_iter=5,

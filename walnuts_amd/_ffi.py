@@ -43,13 +43,34 @@ class Config(C.Structure):
     ]
 
 
+_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
+
+class Observations(C.Structure):
+    """wn_observations: host pointers, read during the call that takes it (walnuts_amd._observations fills one)."""
+    _fields_ = [
+        ("x", _dp),
+        ("y", _dp),
+        ("num_obs", C.c_int),
+        ("group", _i32p),
+        ("num_groups", C.c_int),
+        ("obs_offsets", _i64p),
+        ("num_datasets", C.c_int),
+    ]
+
+
 # every symbol include/walnuts_hip.h declares: (name, restype, argtypes)
 _vp, _sz, _i32, _i64, _u32, _u64, _dbl = C.c_void_p, C.c_size_t, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
-_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-# the reference's trailing sampling arguments (python/src/walnutpie/_ffi.py: _common_sampling_argtypes)
-_REFERENCE_SAMPLING_ARGS = [_sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl,
-                            _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-                            C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]
+_obsp = C.POINTER(Observations)
+# the arguments from `inits` to `print` that every walnutpie_sample_device* entry point takes (the header's sampling list)
+_SAMPLING_ARGS = [_dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl,
+                  _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int), _dp,
+                  _dp, _i32, PRINT_CALLBACK]
+# the reference's trailing sampling arguments (python/src/walnutpie/_ffi.py: _common_sampling_argtypes): from num_chains
+_REFERENCE_SAMPLING_ARGS = _SAMPLING_ARGS[1:] + [_errpp]
+_MODEL_ARGS = [_i32, _dp, _i32]  # model, model_params, num_params
+_RESIDENT_ARGS = [_i32, C.POINTER(_vp)]  # thin, chains_out
+_DEVICES_ARGS = [C.POINTER(C.c_int), _i32]  # devices, num_devices
 LOGP_CFUNC = C.CFUNCTYPE(C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                          C.c_void_p)
 SYMBOLS = [
@@ -62,65 +83,18 @@ SYMBOLS = [
     ("walnutpie_sample_bridgestan", _i32, [C.c_char_p, C.c_char_p, PRINT_CALLBACK, C.c_uint, C.c_char_p]
      + _REFERENCE_SAMPLING_ARGS),
     ("walnutpie_separator_char", C.c_char, []),
-    ("walnutpie_sample_device", _i32,
-     [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
-      _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
-    ("walnutpie_sample_device_reference_streams", _i32,
-     [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
-      _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
-    ("walnutpie_sample_device_resident", _i32,
-     [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
-      _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
-    # the data-model siblings: x, y, num_obs after num_params
-    ("walnutpie_sample_device_data", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
-    ("walnutpie_sample_device_data_resident", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
-    # ... and over several datasets: x, y, obs_offsets (int64 [G + 1]), num_datasets after num_params
-    ("walnutpie_sample_device_datasets", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32,
-      _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
-    ("walnutpie_sample_device_datasets_resident", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32,
-      _i32, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
-    # ... and for a grouped model: x, y, group (int32), num_groups, then num_obs or obs_offsets, num_datasets
-    ("walnutpie_sample_device_grouped", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
-    ("walnutpie_sample_device_grouped_resident", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
-    ("walnutpie_sample_device_grouped_datasets", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _errpp]),
-    ("walnutpie_sample_device_grouped_datasets_resident", _i32,
-     [_i32, _dp, _i32, _dp, _dp, _i32p, _i32, _i64p, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz,
-      C.POINTER(C.c_int), _dp, _dp, _i32, PRINT_CALLBACK, _i32, C.POINTER(_vp), _errpp]),
-    ("walnutpie_sample_device_multi", _i32,
-     [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
-      _dp, _dp, _i32, PRINT_CALLBACK, C.POINTER(C.c_int), _i32, _errpp]),
+    ("walnutpie_sample_device", _i32, _MODEL_ARGS + _SAMPLING_ARGS + [_errpp]),
+    ("walnutpie_sample_device_reference_streams", _i32, _MODEL_ARGS + _SAMPLING_ARGS + [_errpp]),
+    ("walnutpie_sample_device_resident", _i32, _MODEL_ARGS + _SAMPLING_ARGS + _RESIDENT_ARGS + [_errpp]),
+    # the data-model siblings: obs after num_params
+    ("walnutpie_sample_device_observed", _i32, _MODEL_ARGS + [_obsp] + _SAMPLING_ARGS + [_errpp]),
+    ("walnutpie_sample_device_observed_resident", _i32,
+     _MODEL_ARGS + [_obsp] + _SAMPLING_ARGS + _RESIDENT_ARGS + [_errpp]),
+    ("walnutpie_sample_device_multi", _i32, _MODEL_ARGS + _SAMPLING_ARGS + _DEVICES_ARGS + [_errpp]),
     ("walnutpie_sample_device_multi_resident", _i32,
-     [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
-      _dp, _dp, _i32, PRINT_CALLBACK, C.POINTER(C.c_int), _i32, _i32, C.POINTER(_vp), _errpp]),
+     _MODEL_ARGS + _SAMPLING_ARGS + _DEVICES_ARGS + _RESIDENT_ARGS + [_errpp]),
     ("walnutpie_sample_device_multi_allgather", _i32,
-     [_i32, _dp, _i32, _dp, _sz, C.c_uint, C.c_uint, _dbl, _dp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl,
-      _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl, C.c_bool, _dp, _sz, C.POINTER(C.c_int),
-      _dp, _dp, _i32, PRINT_CALLBACK, C.POINTER(C.c_int), _i32, _i32, C.POINTER(_vp), _errpp]),
+     _MODEL_ARGS + _SAMPLING_ARGS + _DEVICES_ARGS + _RESIDENT_ARGS + [_errpp]),
     ("wn_internal_sqrt_probe", _i32, [_dp, _dp, _sz, _i32]),
     ("wn_internal_count_math_probe", _i32, [_dp, _dp, _dp, _sz, _i32]),
     ("wn_model_data_columns", _i32, [_i32, _i32, _i32]),
@@ -140,13 +114,7 @@ SYMBOLS = [
     ("wn_geometry_for_model", _i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _errpp]),
     ("wn_geometry_candidates", _i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int), _i32, C.POINTER(C.c_int), _errpp]),
     ("wn_engine_create", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _sz, C.POINTER(Config), _errpp]),
-    ("wn_engine_create_with_data", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32, _sz, C.POINTER(Config), _errpp]),
-    ("wn_engine_create_with_datasets", _i32,
-     [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i64p, _i32, _sz, C.POINTER(Config), _errpp]),
-    ("wn_engine_create_with_grouped_data", _i32,
-     [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32p, _i32, _i32, _sz, C.POINTER(Config), _errpp]),
-    ("wn_engine_create_with_grouped_datasets", _i32,
-     [C.POINTER(_vp), _i32, _i32, _dp, _dp, _dp, _i32p, _i32, _i64p, _i32, _sz, C.POINTER(Config), _errpp]),
+    ("wn_engine_create_observed", _i32, [C.POINTER(_vp), _i32, _i32, _dp, _obsp, _sz, C.POINTER(Config), _errpp]),
     ("wn_engine_num_datasets", _i32, [_vp]),
     ("wn_engine_destroy", None, [_vp]),
     ("wn_engine_eval", _i32, [_vp, _dp, _dp, _dp, _errpp]),

@@ -126,10 +126,10 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   __device__ __forceinline__ int num_obs() const { return obs_n; }
   __device__ __forceinline__ void load_row(int n, double (&x)[EPL]) const {
     if constexpr (uses_groups<Model>::value) {
-      // rows of P = num_params - num_groups - 1 columns at stride Dx = data_stride = 128 * ceil(P / 128): slot pair k
+      // rows of P = num_params - num_groups - 1 columns at stride Dx = obs.stride = 128 * ceil(P / 128): slot pair k
       // holds columns [128 k, 128 k + 128), so pairs k >= Dx / 128 are zeros and issue no load (a wave-uniform test)
-      const int nx = P.data_stride / (2 * L);
-      const char* lb = lane_base(obs_x + static_cast<long long>(n) * P.data_stride);
+      const int nx = P.obs.stride / (2 * L);
+      const char* lb = lane_base(obs_x + static_cast<long long>(n) * P.obs.stride);
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
         if (k < nx) {
@@ -147,25 +147,25 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   }
   __device__ __forceinline__ double obs_y(int n) const { return obs_yv[n]; }
   // grouped data models (kUsesGroups): J, wave-uniform, and the group of observation n, in [0, J)
-  __device__ __forceinline__ int num_groups() const { return P.num_groups; }
+  __device__ __forceinline__ int num_groups() const { return P.obs.num_groups; }
   __device__ __forceinline__ int obs_group(int n) const { return obs_gv[n]; }
   // Once per chain, before the model is evaluated for it: chain c of an engine with several datasets reads dataset
   // c / chains_per_dataset (the chain index is wave-uniform: one division and two scalar loads per chain, none per
   // row).  Row offsets are 64-bit, so a block beyond 4 GiB is addressed correctly.
   __device__ __forceinline__ void bind_data(int c) {
     if constexpr (uses_data<Model>::value) {
-      if (P.chains_per_dataset > 0) {
-        const int ds = c / P.chains_per_dataset;
-        const long long first = P.data_offsets[ds];
-        obs_x = P.data_x + first * (uses_groups<Model>::value ? static_cast<long long>(P.data_stride) : kDp);
-        obs_yv = P.data_y + first;
-        if constexpr (uses_groups<Model>::value) obs_gv = P.data_group + first;
-        obs_n = static_cast<int>(P.data_offsets[ds + 1] - first);
+      if (P.obs.chains_per_dataset > 0) {
+        const int ds = c / P.obs.chains_per_dataset;
+        const long long first = P.obs.offsets[ds];
+        obs_x = P.obs.x + first * (uses_groups<Model>::value ? static_cast<long long>(P.obs.stride) : kDp);
+        obs_yv = P.obs.y + first;
+        if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group + first;
+        obs_n = static_cast<int>(P.obs.offsets[ds + 1] - first);
       } else {
-        obs_x = P.data_x;
-        obs_yv = P.data_y;
-        if constexpr (uses_groups<Model>::value) obs_gv = P.data_group;
-        obs_n = P.num_obs;
+        obs_x = P.obs.x;
+        obs_yv = P.obs.y;
+        if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group;
+        obs_n = P.obs.num_obs;
       }
     }
   }

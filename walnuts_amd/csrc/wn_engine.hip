@@ -82,18 +82,15 @@ struct wn_engine {
   // the cross-chain monitors (wn_elementwise.h): run partials, stage-1 sums [G][1 + D] (R-hat: [G][2]; mass averaging:
   // [G][D]), stage-2 results [G][2], and per chain the relative distances of the warmup spread
   DevBuf<double> lp_stats, mon_runs, mon_sums, mon_out, mon_rel_mass, mon_rel_step;
-  DevBuf<double> data_x, data_y;  // a data model's observations: [num_obs][Dp] (rows padded with zeros), [num_obs]
-  int num_obs = 0;
-  // several datasets (wn_engine_create_with_datasets): data_x / data_y hold them one after another, dataset g being rows
-  // [data_offsets[g], data_offsets[g + 1]) and chains [g * k, (g + 1) * k), k = chains_per_dataset; 0 = one shared block
+  // a data model's observations, as the kernels take them (wn_params.h), and the buffers `obs` points into: x
+  // [rows][obs.stride] (rows padded with zeros), y [rows]; with several datasets one after another, dataset g being rows
+  // [offsets[g], offsets[g + 1]) and chains [g * k, (g + 1) * k), k = obs.chains_per_dataset; a grouped model's group
+  // of every row, its x (P = D - J - 1 columns) at the narrower stride 128 * ceil(P / 128)
+  wn::Observations obs{};
+  DevBuf<double> data_x, data_y;
   DevBuf<int64_t> data_offsets;
-  int num_datasets = 1;
-  int chains_per_dataset = 0;
-  // a grouped data model (kUsesGroups): the group of every row, J, and the narrower row stride Dx = 128 * ceil(P / 128)
-  // of its x (P = D - J - 1 columns); data_stride = Dp for every other model
   DevBuf<int32_t> data_group;
-  int num_groups = 0;
-  int data_stride = 0;
+  int num_datasets = 1;
   DevBuf<int32_t> min_micro, depth, rng_draws, failed_ext;
   DevBuf<int64_t> grad_evals;
   DevBuf<uint32_t> counter, error_flags;
@@ -304,14 +301,7 @@ struct wn_engine {
     P.est_mode = (warm && est_pending) ? 1 : 0;
     P.work_counter = counter.p;
     P.error_flags = error_flags.p;
-    P.data_x = data_x.p;
-    P.data_y = data_y.p;
-    P.num_obs = num_obs;
-    P.data_stride = data_stride;
-    P.data_offsets = data_offsets.p;
-    P.chains_per_dataset = chains_per_dataset;
-    P.data_group = data_group.p;
-    P.num_groups = num_groups;
+    P.obs = obs;
     return P;
   }
 
@@ -449,21 +439,8 @@ int required_pool(const wn_config& c) {
   return 4 + 3 * levels + 3 + 3 + 2;
 }
 
-// a data model's observations as the caller hands them over (host memory, row-major; not retained)
-struct HostData {
-  const double* x;  // [num_obs][num_params] -- or, with offsets, [offsets[num_datasets]][num_params]
-  const double* y;  // [num_obs]
-  int num_obs;
-  const int64_t* offsets = nullptr;  // several datasets: dataset g is rows [offsets[g], offsets[g + 1])
-  int num_datasets = 0;              // 0: one block shared by every chain
-  // a grouped data model (kUsesGroups): the group of every row, in [0, num_groups); x then has num_params -
-  // num_groups - 1 columns
-  const int32_t* group = nullptr;
-  int num_groups = 0;
-};
-
 void build_engine(wn_engine& e, int model, int num_params, const double* model_params, size_t num_chains,
-                  const wn_config& cfg, const HostData* data = nullptr) {
+                  const wn_config& cfg, const wn_observations* data = nullptr) {
   if (num_params < 1) throw std::invalid_argument("num_params must be positive");
   if (num_chains < 1) throw std::invalid_argument("num_chains must be positive");
   if (!wn::registry_error().empty()) throw std::invalid_argument(wn::registry_error());
@@ -480,13 +457,13 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   ops.validate(num_params);
   if (ops.uses_data && data == nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model is conditioned on data: create it with "
-                                "wn_engine_create_with_data (x [num_obs][" +
+                                "wn_engine_create_observed (x [num_obs][" +
                                 std::string(ops.scale_param ? "num_params - 1" : "num_params") + "], y [num_obs])");
   if (!ops.uses_data && data != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
   if (ops.uses_groups && data != nullptr && data->group == nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads a group per observation: create it with "
-                                "wn_engine_create_with_grouped_data (x [num_obs][num_params - num_groups - 1], y, group "
+                                "wn_engine_create_observed (x [num_obs][num_params - num_groups - 1], y, group "
                                 "[num_obs] in [0, num_groups))");
   if (!ops.uses_groups && data != nullptr && data->group != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
@@ -501,20 +478,20 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
     cols = num_params - J - 1;
   }
   size_t total_obs = 0;  // rows of the observation block
-  if (data != nullptr && data->offsets != nullptr) {
+  if (data != nullptr && data->obs_offsets != nullptr) {
     const int G = data->num_datasets;
     if (G < 1) throw std::invalid_argument("num_datasets must be positive");
     if (num_chains % static_cast<size_t>(G) != 0)
       throw std::invalid_argument("num_chains must be a multiple of num_datasets (chain c reads dataset c / (num_chains / "
                                   "num_datasets))");
-    if (data->offsets[0] != 0) throw std::invalid_argument("obs_offsets must start at 0");
+    if (data->obs_offsets[0] != 0) throw std::invalid_argument("obs_offsets must start at 0");
     for (int g = 0; g < G; ++g) {
-      const int64_t n = data->offsets[g + 1] - data->offsets[g];
+      const int64_t n = data->obs_offsets[g + 1] - data->obs_offsets[g];
       if (n < 1)
         throw std::invalid_argument("obs_offsets must be strictly increasing (every dataset needs at least one observation)");
       if (n > INT32_MAX) throw std::invalid_argument("a dataset holds more than 2^31 - 1 observations");
     }
-    total_obs = static_cast<size_t>(data->offsets[G]);
+    total_obs = static_cast<size_t>(data->obs_offsets[G]);
   } else if (data != nullptr) {
     if (data->num_obs < 1) throw std::invalid_argument("num_obs must be positive");
     total_obs = static_cast<size_t>(data->num_obs);
@@ -531,14 +508,14 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
         if (data->group[i] < 0 || data->group[i] >= data->num_groups)
           throw std::invalid_argument("every group must be in [0, num_groups), observation " + std::to_string(i) + " has " +
                                       std::to_string(data->group[i]));
-    if (data->offsets == nullptr) {
+    if (data->obs_offsets == nullptr) {
       ops.host_data(data->x, data->y, data->num_obs, cols);
     } else {
       for (int g = 0; g < data->num_datasets; ++g) {
-        const int64_t first = data->offsets[g];
+        const int64_t first = data->obs_offsets[g];
         try {
           ops.host_data(data->x + static_cast<size_t>(first) * cols, data->y + first,
-                        static_cast<int>(data->offsets[g + 1] - first), cols);
+                        static_cast<int>(data->obs_offsets[g + 1] - first), cols);
         } catch (const std::invalid_argument& ex) {
           throw std::invalid_argument("dataset " + std::to_string(g) + ": " + ex.what());
         }
@@ -690,45 +667,42 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   }
   // rows padded with zeros to the stride Dx: Dp, the layout of a theta row (lane tid's slot j holds coordinate index(j));
   // for a grouped model 128 * ceil(P / 128), the slot pairs of theta that hold x's P columns
-  e.data_stride = ops.uses_groups ? 128 * ((cols + 127) / 128) : e.Dp;
-  if (data != nullptr && data->group != nullptr) {
-    e.num_groups = data->num_groups;
-    e.data_group.alloc(total_obs);
-    HIP_OK(hipMemcpyAsync(e.data_group.p, data->group, total_obs * sizeof(int32_t), hipMemcpyHostToDevice, e.stream));
-  }
-  if (data != nullptr && data->offsets == nullptr) {
-    const size_t N = static_cast<size_t>(data->num_obs), Dx = static_cast<size_t>(e.data_stride);
-    std::vector<double> xp(N * Dx, 0.0);
-    for (size_t n = 0; n < N; ++n) std::memcpy(&xp[n * Dx], data->x + n * cols, sizeof(double) * cols);
-    e.data_x.alloc(xp.size());
+  e.obs.stride = ops.uses_groups ? 128 * ((cols + 127) / 128) : e.Dp;
+  if (data != nullptr) {
+    // the padded copy goes up in slices of at most 64 MiB (a block of many datasets may be larger than what is
+    // sensible to double in host memory)
+    const size_t N = total_obs, Dx = static_cast<size_t>(e.obs.stride);
+    e.data_x.alloc(N * Dx);
     e.data_y.alloc(N);
-    e.num_obs = data->num_obs;
-    HIP_OK(hipMemcpyAsync(e.data_x.p, xp.data(), xp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
-    HIP_OK(hipMemcpyAsync(e.data_y.p, data->y, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
-    HIP_OK(hipStreamSynchronize(e.stream));
-  } else if (data != nullptr) {
-    // the datasets one after another, rows padded as above; the padded copy goes up in slices of at most 64 MiB (a
-    // block of many datasets may be larger than what is sensible to double in host memory)
-    const size_t N = total_obs, Dp = static_cast<size_t>(e.data_stride);  // (the row stride Dx)
-    const int G = data->num_datasets;
-    e.data_x.alloc(N * Dp);
-    e.data_y.alloc(N);
-    e.data_offsets.alloc(static_cast<size_t>(G) + 1);
-    e.num_obs = 0;  // (per dataset: data_offsets)
-    e.num_datasets = G;
-    e.chains_per_dataset = static_cast<int>(num_chains / static_cast<size_t>(G));
-    const size_t slice = std::max<size_t>(1, (size_t{64} << 20) / (Dp * sizeof(double)));
-    std::vector<double> xp(std::min(N, slice) * Dp, 0.0);
+    const size_t slice = std::max<size_t>(1, (size_t{64} << 20) / (Dx * sizeof(double)));
+    std::vector<double> xp(std::min(N, slice) * Dx, 0.0);
     for (size_t n0 = 0; n0 < N; n0 += slice) {
       const size_t rows = std::min(slice, N - n0);
       for (size_t n = 0; n < rows; ++n)
-        std::memcpy(&xp[n * Dp], data->x + (n0 + n) * cols, sizeof(double) * cols);
-      HIP_OK(hipMemcpyAsync(e.data_x.p + n0 * Dp, xp.data(), rows * Dp * sizeof(double), hipMemcpyHostToDevice, e.stream));
+        std::memcpy(&xp[n * Dx], data->x + (n0 + n) * cols, sizeof(double) * cols);
+      HIP_OK(hipMemcpyAsync(e.data_x.p + n0 * Dx, xp.data(), rows * Dx * sizeof(double), hipMemcpyHostToDevice, e.stream));
       HIP_OK(hipStreamSynchronize(e.stream));  // (before the staging slice is refilled)
     }
     HIP_OK(hipMemcpyAsync(e.data_y.p, data->y, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
-    HIP_OK(hipMemcpyAsync(e.data_offsets.p, data->offsets, (static_cast<size_t>(G) + 1) * sizeof(int64_t),
-                          hipMemcpyHostToDevice, e.stream));
+    e.obs.x = e.data_x.p;
+    e.obs.y = e.data_y.p;
+    if (data->group != nullptr) {
+      e.data_group.alloc(N);
+      HIP_OK(hipMemcpyAsync(e.data_group.p, data->group, N * sizeof(int32_t), hipMemcpyHostToDevice, e.stream));
+      e.obs.group = e.data_group.p;
+      e.obs.num_groups = data->num_groups;
+    }
+    if (data->obs_offsets != nullptr) {
+      // the datasets one after another; the kernels take every chain's row count from the offsets (obs.num_obs = 0)
+      const size_t G = static_cast<size_t>(data->num_datasets);
+      e.data_offsets.alloc(G + 1);
+      HIP_OK(hipMemcpyAsync(e.data_offsets.p, data->obs_offsets, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, e.stream));
+      e.obs.offsets = e.data_offsets.p;
+      e.obs.chains_per_dataset = static_cast<int>(num_chains / G);
+      e.num_datasets = data->num_datasets;
+    } else {
+      e.obs.num_obs = data->num_obs;
+    }
     HIP_OK(hipStreamSynchronize(e.stream));
   }
   {
@@ -765,14 +739,7 @@ void run_init(wn_engine& e, bool pos, bool masses, bool step, double scale, doub
   Q.step_seed = step_seed;
   Q.pos_chain_offset = pos_off;
   Q.step_chain_offset = step_off;
-  Q.data_x = e.data_x.p;
-  Q.data_y = e.data_y.p;
-  Q.num_obs = e.num_obs;
-  Q.data_stride = e.data_stride;
-  Q.data_offsets = e.data_offsets.p;
-  Q.chains_per_dataset = e.chains_per_dataset;
-  Q.data_group = e.data_group.p;
-  Q.num_groups = e.num_groups;
+  Q.obs = e.obs;
   const int grid = e.geo.mem ? e.grid : static_cast<int>(std::min<size_t>(e.C, static_cast<size_t>(e.num_cus) * 8));
   wn::launch_init(e.model, e.geo, grid, wn::transition_smem_bytes(e.geo.nw, 0, e.Dp), e.stream, Q);
   HIP_OK(hipGetLastError());
@@ -968,57 +935,12 @@ int wn_engine_create(wn_engine** out, int model, int num_params, const double* m
     *out = e.release();
   });
 }
-int wn_engine_create_with_data(wn_engine** out, int model, int num_params, const double* model_params,
-                               const double* x, const double* y, int num_obs, size_t num_chains, const wn_config* cfg,
-                               WalnutpyError** err) {
+int wn_engine_create_observed(wn_engine** out, int model, int num_params, const double* model_params,
+                              const wn_observations* obs, size_t num_chains, const wn_config* cfg, WalnutpyError** err) {
   return guarded(err, [&] {
-    if (out == nullptr || cfg == nullptr) throw std::invalid_argument("null argument");
-    const HostData data{x, y, num_obs};
+    if (out == nullptr || cfg == nullptr || obs == nullptr) throw std::invalid_argument("null argument");
     auto e = std::make_unique<wn_engine>();
-    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
-    *out = e.release();
-  });
-}
-int wn_engine_create_with_datasets(wn_engine** out, int model, int num_params, const double* model_params,
-                                   const double* x, const double* y, const int64_t* obs_offsets, int num_datasets,
-                                   size_t num_chains, const wn_config* cfg, WalnutpyError** err) {
-  return guarded(err, [&] {
-    if (out == nullptr || cfg == nullptr || obs_offsets == nullptr) throw std::invalid_argument("null argument");
-    HostData data{x, y, 0};
-    data.offsets = obs_offsets;
-    data.num_datasets = num_datasets;
-    auto e = std::make_unique<wn_engine>();
-    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
-    *out = e.release();
-  });
-}
-int wn_engine_create_with_grouped_data(wn_engine** out, int model, int num_params, const double* model_params,
-                                       const double* x, const double* y, const int32_t* group, int num_groups, int num_obs,
-                                       size_t num_chains, const wn_config* cfg, WalnutpyError** err) {
-  return guarded(err, [&] {
-    if (out == nullptr || cfg == nullptr || group == nullptr) throw std::invalid_argument("null argument");
-    HostData data{x, y, num_obs};
-    data.group = group;
-    data.num_groups = num_groups;
-    auto e = std::make_unique<wn_engine>();
-    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
-    *out = e.release();
-  });
-}
-int wn_engine_create_with_grouped_datasets(wn_engine** out, int model, int num_params, const double* model_params,
-                                           const double* x, const double* y, const int32_t* group, int num_groups,
-                                           const int64_t* obs_offsets, int num_datasets, size_t num_chains,
-                                           const wn_config* cfg, WalnutpyError** err) {
-  return guarded(err, [&] {
-    if (out == nullptr || cfg == nullptr || obs_offsets == nullptr || group == nullptr)
-      throw std::invalid_argument("null argument");
-    HostData data{x, y, 0};
-    data.offsets = obs_offsets;
-    data.num_datasets = num_datasets;
-    data.group = group;
-    data.num_groups = num_groups;
-    auto e = std::make_unique<wn_engine>();
-    build_engine(*e, model, num_params, model_params, num_chains, *cfg, &data);
+    build_engine(*e, model, num_params, model_params, num_chains, *cfg, obs);
     *out = e.release();
   });
 }
@@ -1047,14 +969,7 @@ int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* 
     Q.model_params = e->model_params.p;
     Q.scratch = e->arena.p;
     Q.scratch_stride = e->arena_stride;
-    Q.data_x = e->data_x.p;
-    Q.data_y = e->data_y.p;
-    Q.num_obs = e->num_obs;
-    Q.data_stride = e->data_stride;
-    Q.data_offsets = e->data_offsets.p;
-    Q.chains_per_dataset = e->chains_per_dataset;
-    Q.data_group = e->data_group.p;
-    Q.num_groups = e->num_groups;
+    Q.obs = e->obs;
     Q.logp_out = lp.p;
     Q.grad_out = grad.p;
     const int grid = e->geo.mem ? e->grid : static_cast<int>(std::min<size_t>(C, static_cast<size_t>(e->num_cus) * 8));
@@ -1411,8 +1326,8 @@ void average_masses_segments(wn_engine& e, int G, int k) {
 }
 
 void require_datasets(const wn_engine* e) {
-  if (e->chains_per_dataset == 0)
-    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_with_datasets)");
+  if (e->obs.chains_per_dataset == 0)
+    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_observed with obs_offsets)");
 }
 }  // namespace
 
@@ -1481,7 +1396,7 @@ int wn_engine_rhat_datasets(wn_engine* e, double* rhat, WalnutpyError** err) {
   return guarded(err, [&] {
     if (rhat == nullptr) throw std::invalid_argument("null argument");
     require_datasets(e);
-    rhat_segments(*e, e->num_datasets, e->chains_per_dataset, rhat);
+    rhat_segments(*e, e->num_datasets, e->obs.chains_per_dataset, rhat);
   });
 }
 int wn_engine_warmup_spread_datasets(wn_engine* e, double* max_rel_diff_step, double* max_rel_diff_mass,
@@ -1489,13 +1404,13 @@ int wn_engine_warmup_spread_datasets(wn_engine* e, double* max_rel_diff_step, do
   return guarded(err, [&] {
     if (max_rel_diff_step == nullptr || max_rel_diff_mass == nullptr) throw std::invalid_argument("null argument");
     require_datasets(e);
-    warmup_spread_segments(*e, e->num_datasets, e->chains_per_dataset, max_rel_diff_step, max_rel_diff_mass);
+    warmup_spread_segments(*e, e->num_datasets, e->obs.chains_per_dataset, max_rel_diff_step, max_rel_diff_mass);
   });
 }
 int wn_engine_average_masses_datasets(wn_engine* e, WalnutpyError** err) {
   return guarded(err, [&] {
     require_datasets(e);
-    average_masses_segments(*e, e->num_datasets, e->chains_per_dataset);
+    average_masses_segments(*e, e->num_datasets, e->obs.chains_per_dataset);
   });
 }
 // The driver's one-shard controller looks (wn_sample.hip): per dataset, or pooled on an engine without datasets

@@ -24,15 +24,7 @@ struct InitParams {
   double scale, smoothing;
   uint64_t pos_seed, step_seed;
   uint32_t pos_chain_offset, step_chain_offset;
-  // a data model's observations (Params::data_x ...)
-  const double* data_x;
-  const double* data_y;
-  int32_t num_obs;
-  int32_t data_stride;
-  const int64_t* data_offsets;
-  int32_t chains_per_dataset;
-  const int32_t* data_group;
-  int32_t num_groups;
+  Observations obs;  // a data model's observations
   // eval_kernel (wn_engine_eval): the model's log density [C] and gradient [C][Dp] at theta
   double* logp_out;
   double* grad_out;
@@ -47,14 +39,7 @@ __global__ __launch_bounds__(64 * NW) void init_kernel(const InitParams Q) {
   P.dim = Q.dim;
   P.dim_padded = Q.dim_padded;
   P.model_params = Q.model_params;
-  P.data_x = Q.data_x;
-  P.data_y = Q.data_y;
-  P.num_obs = Q.num_obs;
-  P.data_stride = Q.data_stride;
-  P.data_offsets = Q.data_offsets;
-  P.chains_per_dataset = Q.chains_per_dataset;
-  P.data_group = Q.data_group;
-  P.num_groups = Q.num_groups;
+  P.obs = Q.obs;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;
@@ -159,14 +144,7 @@ __global__ __launch_bounds__(64 * NW) void eval_kernel(const InitParams Q) {
   P.dim = Q.dim;
   P.dim_padded = Q.dim_padded;
   P.model_params = Q.model_params;
-  P.data_x = Q.data_x;
-  P.data_y = Q.data_y;
-  P.num_obs = Q.num_obs;
-  P.data_stride = Q.data_stride;
-  P.data_offsets = Q.data_offsets;
-  P.chains_per_dataset = Q.chains_per_dataset;
-  P.data_group = Q.data_group;
-  P.num_groups = Q.num_groups;
+  P.obs = Q.obs;
   WN_LDS double* base = (WN_LDS double*)smem;
   WN_LDS typename T::Meta* meta = (WN_LDS typename T::Meta*)(base + wave_in_workgroup() * kMetaDoubles);
   WN_LDS double* red = base + NW * kMetaDoubles;

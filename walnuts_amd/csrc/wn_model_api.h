@@ -55,15 +55,15 @@
 //     static constexpr int preferred_elems_per_lane(int num_params);
 //
 //     // optional -- a model CONDITIONED ON DATA: the engine keeps a read-only observation block in HBM (x: num_obs rows
-//     // of num_params doubles, y: num_obs doubles; wn_engine_create_with_data / walnutpie_sample_device_data*), and
+//     // of num_params doubles, y: num_obs doubles; wn_engine_create_observed / walnutpie_sample_device_observed*), and
 //     // eval() reads it through the cx calls below.  A data model runs one wavefront per chain on the register kernels
 //     // (1 <= num_params <= 1024, any num_obs >= 1): it declares no streaming form, and wn_engine_create refuses other
 //     // geometries, a data model without data and data for a model without this member (`config` errors).
 //     static constexpr bool kUsesData = true;
 //     static void host_data(const double* x, const double* y, int num_obs, int num_params);  // optional checks (throw)
-//     // ... and, on top of kUsesData, a GROUP per observation (int32 in [0, J), copied beside y;
-//     // wn_engine_create_with_grouped_data / walnutpie_sample_device_grouped*): x then has P = num_params - J - 1
-//     // columns, stored at the narrower row stride Dx = 128 * ceil(P / 128) (host_data's last argument is P).
+//     // ... and, on top of kUsesData, a GROUP per observation (int32 in [0, J), copied beside y; wn_observations::group,
+//     // num_groups): x then has P = num_params - J - 1 columns, stored at the narrower row stride
+//     // Dx = 128 * ceil(P / 128) (host_data's last argument is P).
 //     // wn_engine_create refuses a grouped model without groups and groups for a model without this member.
 //     static constexpr bool kUsesGroups = true;
 //     // ... or, on top of kUsesData and NOT with kUsesGroups (a static_assert), a SCALE PARAMETER as the last
@@ -84,7 +84,7 @@
 //                                             wn_config::fused_multiply_add, a rounded product plus an add otherwise
 // ... and, compiled in for data models only (kUsesData; one wavefront per chain, so Cx::L == 64).  They are relative to
 // the CHAIN's dataset: the engine's one block, or -- an engine built with several datasets
-// (wn_engine_create_with_datasets) -- the block of the dataset the chain is conditioned on; the model cannot tell:
+// (wn_observations::obs_offsets) -- the block of the dataset the chain is conditioned on; the model cannot tell:
 //   cx.num_obs()                              number of observations, wave-uniform
 //   cx.load_row(n, x)                         double x[EPL] = the lane's slots of row n of x: slot j holds column
 //                                             cx.index(j), zero beyond num_params (a row is laid out like theta and

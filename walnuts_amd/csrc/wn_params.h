@@ -1,6 +1,7 @@
 // wn_params.h -- plain-data launch parameters shared by the host side (wn_capi.cpp) and the kernels.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 namespace wn {
@@ -21,6 +22,24 @@ constexpr int kMetaDoubles = 128;
 
 enum ModelKind : int32_t { kStdNormal = 0, kDiagNormal = 1, kFunnel = 2 };
 enum RngMode : int32_t { kRngPhilox = 0, kRngBuffer = 1 };
+
+// The observations of a data model (wn_model_api.h, kUsesData; null / 0 otherwise), read-only device memory shared by
+// every chain: what TrajChip::bind_data / load_row / obs_y / obs_group read.
+struct Observations {
+  // x is num_obs rows of stride (= Dp) doubles, each laid out like a theta row and zero beyond num_params
+  const double* x;
+  const double* y;  // [num_obs]
+  int32_t num_obs;
+  int32_t stride;
+  // several datasets (wn_observations::obs_offsets): chain c reads dataset c / chains_per_dataset, rows
+  // [offsets[g], offsets[g + 1]) of x / y; chains_per_dataset = 0: one block shared by every chain
+  const int64_t* offsets;  // [G + 1]
+  int32_t chains_per_dataset;
+  // grouped data models (kUsesGroups): the group of every observation, in [0, num_groups), sliced like y.  Their
+  // rows are narrower than theta: stride = 128 * ceil(P / 128) doubles for P = num_params - num_groups - 1 columns
+  const int32_t* group;  // [num_obs] (null for other models)
+  int32_t num_groups;
+};
 
 // Every [C][Dp] plane is chain-major: one chain's vector is contiguous, rows are
 // padded to Dp = 64*NW*EPL doubles so that lane l of the chain's workgroup owns
@@ -92,21 +111,12 @@ struct Params {
                           // previous launch's last transition yet (this launch's first prologue applies the observation);
                           // 2 = apply that observation and do nothing else (the engine's flush); 0 = nothing pending
   uint32_t* error_flags;  // OR of kErr* bits of every chain and transition since wn_engine_check last read (and cleared) it
-  // observations of a data model (wn_model_api.h, kUsesData; null / 0 otherwise), read-only and shared by every chain:
-  // data_x is num_obs rows of data_stride (= Dp) doubles, each laid out like a theta row and zero beyond num_params
-  const double* data_x;
-  const double* data_y;  // [num_obs]
-  int32_t num_obs;
-  int32_t data_stride;
-  // several datasets (wn_engine_create_with_datasets): chain c reads dataset c / chains_per_dataset, rows
-  // [data_offsets[g], data_offsets[g + 1]) of data_x / data_y; chains_per_dataset = 0: one block shared by every chain
-  const int64_t* data_offsets;  // [G + 1]
-  int32_t chains_per_dataset;
-  // grouped data models (kUsesGroups): the group of every observation, in [0, num_groups), sliced like data_y.  Their
-  // rows are narrower than theta: data_stride = 128 * ceil(P / 128) doubles for P = num_params - num_groups - 1 columns
-  const int32_t* data_group;  // [num_obs] (null for other models)
-  int32_t num_groups;
+  Observations obs;       // a data model's observations (null / 0 for other models)
 };
+// The layout the device models were compiled against (ModelAbi::sizeof_params, wn_model_api.h: kModelAbiVersion): a
+// change that moves these is a new ABI version.
+static_assert(sizeof(Observations) == 56 && sizeof(Params) == 448 && offsetof(Params, obs) == 392,
+              "wn::Params changed its layout: bump kModelAbiVersion");
 
 enum : uint32_t {
   kErrPoolExhausted = 1u,     // a chain needed more span-pool vectors than the engine holds

@@ -838,25 +838,10 @@ struct ResidentRequest {  // walnutpie_sample_device*_resident, _multi_allgather
   wn_chains** chains_out;
   bool all_gather = false;  // multi-device: chains_out is an array of num_devices handles, every device gets the whole block
 };
-// a data model's observations (walnutpie_sample_device_data*): host pointers, copied by wn_engine_create_with_data --
-// or, walnutpie_sample_device_datasets*, several datasets one after another, copied by wn_engine_create_with_datasets
-struct SampleData {
-  const double* x;  // [num_obs][num_params]
-  const double* y;  // [num_obs]
-  int num_obs;
-  bool several = false;              // walnutpie_sample_device_datasets*: the two fields below describe the datasets
-  const int64_t* offsets = nullptr;  // dataset g is rows [offsets[g], offsets[g + 1])
-  int num_datasets = 0;
-  // walnutpie_sample_device_grouped*: the group of every row (a grouped model: kUsesGroups), copied by
-  // wn_engine_create_with_grouped_data / _datasets
-  bool grouped = false;
-  const int32_t* group = nullptr;
-  int num_groups = 0;
-};
 struct Mode {
   bool reference_streams = false;            // walnutpie_sample_device_reference_streams
   const ResidentRequest* resident = nullptr;
-  const SampleData* data = nullptr;
+  const wn_observations* obs = nullptr;      // walnutpie_sample_device_observed*: host pointers, copied by the engine
 };
 
 // ---- validation, once per call, before any engine exists ------------------------------------------------------------
@@ -1118,20 +1103,8 @@ void run_shard(const Model& m, const SampleArgs& a, const Mode& mode, const Plan
   // started once the device allocations are done -- see below)
   std::unique_ptr<Prefault> populate;
   EngineGuard guard;
-  if (mode.data != nullptr && mode.data->grouped && mode.data->several) {
-    WN_CALL(wn_engine_create_with_grouped_datasets(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
-                                                   mode.data->group, mode.data->num_groups, mode.data->offsets,
-                                                   mode.data->num_datasets, C, &plan.cfg, &call_err_));
-  } else if (mode.data != nullptr && mode.data->grouped) {
-    WN_CALL(wn_engine_create_with_grouped_data(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
-                                               mode.data->group, mode.data->num_groups, mode.data->num_obs, C,
-                                               &plan.cfg, &call_err_));
-  } else if (mode.data != nullptr && mode.data->several) {
-    WN_CALL(wn_engine_create_with_datasets(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
-                                           mode.data->offsets, mode.data->num_datasets, C, &plan.cfg, &call_err_));
-  } else if (mode.data != nullptr) {
-    WN_CALL(wn_engine_create_with_data(&guard.e, m.id, m.num_params, m.params, mode.data->x, mode.data->y,
-                                       mode.data->num_obs, C, &plan.cfg, &call_err_));
+  if (mode.obs != nullptr) {
+    WN_CALL(wn_engine_create_observed(&guard.e, m.id, m.num_params, m.params, mode.obs, C, &plan.cfg, &call_err_));
   } else {
     WN_CALL(wn_engine_create(&guard.e, m.id, m.num_params, m.params, C, &plan.cfg, &call_err_));
   }
@@ -1433,77 +1406,27 @@ extern "C" int walnutpie_sample_device_resident(int model, const double* model_p
   const ResidentRequest req{thin, chains_out};
   return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req}, err);
 }
-// the same two calls for a model conditioned on data (x, y, num_obs after num_params)
-extern "C" int walnutpie_sample_device_data(int model, const double* model_params, int num_params, const double* x,
-                                            const double* y, int num_obs, WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
-  const SampleData data{x, y, num_obs};
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
+// the same two calls for a model conditioned on data (obs after num_params; include/walnuts_hip.h: wn_observations)
+namespace {
+int sample_observed(const Model& m, const wn_observations* obs, const SampleArgs& a, const ResidentRequest* resident,
+                    WalnutpyError** err) {
+  if (obs == nullptr) {  // (Mode::obs == nullptr stands for a model without data)
+    if (err) *err = static_cast<WalnutpyError*>(wn_internal_make_error("null argument", config));
+    return -1;
+  }
+  return sample_one(m, a, Mode{false, resident, obs}, err);
 }
-extern "C" int walnutpie_sample_device_data_resident(int model, const double* model_params, int num_params,
-                                                     const double* x, const double* y, int num_obs,
-                                                     WN_SAMPLE_ARG_LIST(WN_PARAM) int thin, wn_chains** chains_out,
-                                                     WalnutpyError** err) {
-  const ResidentRequest req{thin, chains_out};
-  const SampleData data{x, y, num_obs};
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
+}  // namespace
+extern "C" int walnutpie_sample_device_observed(int model, const double* model_params, int num_params,
+                                                const wn_observations* obs, WN_SAMPLE_ARG_LIST(WN_PARAM)
+                                                    WalnutpyError** err) {
+  return sample_observed({model, model_params, num_params}, obs, {WN_SAMPLE_ARG_LIST(WN_NAME)}, nullptr, err);
 }
-// ... and for several datasets (obs_offsets, num_datasets after y): chains [g * k, (g + 1) * k) on dataset g
-extern "C" int walnutpie_sample_device_datasets(int model, const double* model_params, int num_params, const double* x,
-                                                const double* y, const int64_t* obs_offsets, int num_datasets,
-                                                WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
-  const SampleData data{x, y, 0, true, obs_offsets, num_datasets};
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
-}
-extern "C" int walnutpie_sample_device_datasets_resident(int model, const double* model_params, int num_params,
-                                                         const double* x, const double* y, const int64_t* obs_offsets,
-                                                         int num_datasets, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
+extern "C" int walnutpie_sample_device_observed_resident(int model, const double* model_params, int num_params,
+                                                         const wn_observations* obs, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
                                                          wn_chains** chains_out, WalnutpyError** err) {
   const ResidentRequest req{thin, chains_out};
-  const SampleData data{x, y, 0, true, obs_offsets, num_datasets};
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
-}
-// ... and for a grouped model (walnuts_amd/csrc/models/hier_glm.h: group, num_groups after y), one block or several
-extern "C" int walnutpie_sample_device_grouped(int model, const double* model_params, int num_params, const double* x,
-                                               const double* y, const int32_t* group, int num_groups, int num_obs,
-                                               WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
-  SampleData data{x, y, num_obs};
-  data.grouped = true;
-  data.group = group;
-  data.num_groups = num_groups;
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
-}
-extern "C" int walnutpie_sample_device_grouped_resident(int model, const double* model_params, int num_params,
-                                                        const double* x, const double* y, const int32_t* group,
-                                                        int num_groups, int num_obs, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
-                                                        wn_chains** chains_out, WalnutpyError** err) {
-  const ResidentRequest req{thin, chains_out};
-  SampleData data{x, y, num_obs};
-  data.grouped = true;
-  data.group = group;
-  data.num_groups = num_groups;
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
-}
-extern "C" int walnutpie_sample_device_grouped_datasets(int model, const double* model_params, int num_params,
-                                                        const double* x, const double* y, const int32_t* group,
-                                                        int num_groups, const int64_t* obs_offsets, int num_datasets,
-                                                        WN_SAMPLE_ARG_LIST(WN_PARAM) WalnutpyError** err) {
-  SampleData data{x, y, 0, true, obs_offsets, num_datasets};
-  data.grouped = true;
-  data.group = group;
-  data.num_groups = num_groups;
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, nullptr, &data}, err);
-}
-extern "C" int walnutpie_sample_device_grouped_datasets_resident(int model, const double* model_params, int num_params,
-                                                                 const double* x, const double* y, const int32_t* group,
-                                                                 int num_groups, const int64_t* obs_offsets,
-                                                                 int num_datasets, WN_SAMPLE_ARG_LIST(WN_PARAM) int thin,
-                                                                 wn_chains** chains_out, WalnutpyError** err) {
-  const ResidentRequest req{thin, chains_out};
-  SampleData data{x, y, 0, true, obs_offsets, num_datasets};
-  data.grouped = true;
-  data.group = group;
-  data.num_groups = num_groups;
-  return sample_one({model, model_params, num_params}, {WN_SAMPLE_ARG_LIST(WN_NAME)}, Mode{false, &req, &data}, err);
+  return sample_observed({model, model_params, num_params}, obs, {WN_SAMPLE_ARG_LIST(WN_NAME)}, &req, err);
 }
 extern "C" int walnutpie_sample_device_multi(int model, const double* model_params, int num_params,
                                              WN_SAMPLE_ARG_LIST(WN_PARAM) const int* devices, int num_devices,

@@ -11,6 +11,7 @@ from typing import Generic, Optional, TypeVar
 import numpy as np
 
 from . import _ffi
+from ._observations import observations
 
 T = TypeVar("T")
 
@@ -157,12 +158,12 @@ def walnuts_device(
     with ``all_gather=True`` as well (walnutpie_sample_device_multi_allgather) EVERY listed device ends with the whole
     block -- the call returns ``(results, [chains on devices[0], chains on devices[1], ...])``.
 
-    ``data=(x, y)`` (walnutpie_sample_device_data / _data_resident): the observations of a model conditioned on data
+    ``data=(x, y)`` (walnutpie_sample_device_observed / _observed_resident): the observations of a model conditioned on data
     (``MODEL_LINEAR_REGRESSION``, ``MODEL_LOGISTIC_REGRESSION``, the count models below or a model of your own that
     declares ``kUsesData``), ``x`` of shape (num_obs, num_params) and ``y`` of shape (num_obs,); copied to the device once.  One device only:
     not with ``devices`` or ``reference_streams``.
 
-    ``data=(x, y, group)`` (walnutpie_sample_device_grouped / _grouped_resident): a grouped model (MODEL_HIER_*), x of
+    ``data=(x, y, group)``: a grouped model (MODEL_HIER_*), x of
     shape (num_obs, P), groups in [0, J), J = num_params - P - 1; ``datasets=`` then takes triples (x, y, group).
 
     Count models and an estimated noise level: ``MODEL_POISSON_REGRESSION`` takes data as the linear and logistic
@@ -170,7 +171,7 @@ def walnuts_device(
     their x has num_params - 1 columns and ``model_params`` is [prior variances of beta | sigma_0];
     ``MODEL_HIER_POISSON_REGRESSION`` and ``_CENTERED`` take (x, y, group) as the other MODEL_HIER_* models.
 
-    ``datasets=[(x0, y0), (x1, y1), ...]`` (walnutpie_sample_device_datasets / _datasets_resident): G datasets of the
+    ``datasets=[(x0, y0), (x1, y1), ...]`` (wn_observations::obs_offsets): G datasets of the
     same model and prior, fitted in one run.  ``num_chains`` (the total) must be a multiple k of G; chains
     [g*k, (g+1)*k) are conditioned on dataset g, and the results list is per chain as usual.  Warmup and sampling stop
     when EVERY dataset meets the rules (spread per dataset, R-hat per dataset).  With ``keep_on_device=True`` the call
@@ -210,30 +211,8 @@ def walnuts_device(
         raise ValueError("At least one of num_params or inits must be specified")
     if seed is None:
         seed = int(np.random.randint(0, 2**32 - 1, dtype=np.uint32))
-    data_args = ()
-    grouped = False
-    from .engine import _is_grouped
-
-    if data is not None and _is_grouped(data):
-        from .engine import _grouped_arrays
-
-        x, y, grp, J = _grouped_arrays(data, num_params)
-        grouped = True
-        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), grp.ctypes.data_as(_ffi._i32p), J, y.size)
-    elif data is not None:
-        from .engine import _data_arrays, _data_columns
-
-        x, y = _data_arrays(data, _data_columns(lib, model, num_params))
-        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp), y.size)
-    num_datasets = 1
-    if datasets is not None:
-        from .engine import _data_columns, _datasets_arrays
-
-        x, y, offsets, grp, J = _datasets_arrays(datasets, num_params, _data_columns(lib, model, num_params))
-        num_datasets = offsets.size - 1
-        grouped = grp is not None
-        data_args = (x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp)) + (
-            (grp.ctypes.data_as(_ffi._i32p), J) if grouped else ()) + (offsets.ctypes.data_as(_ffi._i64p), num_datasets)
+    obs = observations(lib, model, num_params, data, datasets)
+    num_datasets = obs.num_datasets if datasets is not None else 1
     mp = None if model_params is None else np.ascontiguousarray(np.asarray(model_params, dtype=np.float64))
     if mp is not None and mp.size != num_params:
         raise ValueError("model_params must have num_params entries")
@@ -267,15 +246,8 @@ def walnuts_device(
     if keep_on_device:
         entry = lib.walnutpie_sample_device_resident
         tail = (refresh, cb, thin, C.byref(chains_handle), C.byref(err))
-    if data is not None:
-        entry = lib.walnutpie_sample_device_data_resident if keep_on_device else lib.walnutpie_sample_device_data
-        if grouped:
-            entry = lib.walnutpie_sample_device_grouped_resident if keep_on_device else lib.walnutpie_sample_device_grouped
-    if datasets is not None:
-        entry = lib.walnutpie_sample_device_datasets_resident if keep_on_device else lib.walnutpie_sample_device_datasets
-        if grouped:
-            entry = (lib.walnutpie_sample_device_grouped_datasets_resident if keep_on_device
-                     else lib.walnutpie_sample_device_grouped_datasets)
+    if obs is not None:
+        entry = lib.walnutpie_sample_device_observed_resident if keep_on_device else lib.walnutpie_sample_device_observed
     if devices is not None:
         dev = (C.c_int * len(devices))(*[int(d) for d in devices])
         entry = lib.walnutpie_sample_device_multi
@@ -294,7 +266,7 @@ def walnuts_device(
     timing = os.environ.get("WALNUTS_AMD_TIMING") is not None   # the C side prints its phases under the same switch
     t_call = time.perf_counter()
     rc = entry(
-        model, None if mp is None else mp.ctypes.data_as(dp), num_params, *data_args,
+        model, None if mp is None else mp.ctypes.data_as(dp), num_params, *(() if obs is None else (C.byref(obs),)),
         None if inits is None else inits.ctypes.data_as(dp), num_chains, seed, id, init_radius,
         None if inv_metric_init is None else inv_metric_init.ctypes.data_as(dp), min_warmup_iter, max_warmup_iter,
         min_sampling_iter, max_sampling_iter, max_trajectory_doublings, max_step_halvings, min_micro_steps,

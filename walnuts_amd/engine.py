@@ -13,6 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _ffi
+from ._observations import _f64, observations
 
 MODEL_STD_NORMAL, MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_RW1 = 0, 1, 2, 3
 # models conditioned on data (walnuts_amd/csrc/models/glm.h): params = the prior variances, data = (x, y)
@@ -56,114 +57,23 @@ def stream_version(lib_path: Optional[str] = None) -> int:
     return int(_ffi.load_library(lib_path).wn_stream_version())
 
 
-def _f64(a) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-
-
-def _data_columns(lib, model: int, num_params: int) -> int:
-    """Columns of x that the library's data model `model` reads at num_params (wn_model_data_columns): num_params, or
-    num_params - 1 for a model with a scale parameter.  An id that holds no flat data model gives num_params, and the
-    engine then refuses the model (or the pair (x, y) for a grouped model) with its own message."""
-    cols = int(lib.wn_model_data_columns(int(model), int(num_params), 0))
-    return cols if cols >= 0 else int(num_params)
-
-
-def _data_arrays(data, num_params: int):
-    """(x, y) of a data model as contiguous float64 arrays: x (num_obs, num_params), y (num_obs,).  `num_params` is the
-    width x must have: _data_columns() of the model."""
-    try:
-        x, y = data
-    except (TypeError, ValueError):
-        raise ValueError("data must be a pair (x, y)") from None
-    x, y = _f64(x), _f64(y)
-    if x.ndim != 2 or x.shape[1] != num_params:
-        raise ValueError(f"data x must have shape (num_obs, {num_params}), got {x.shape}")
-    if y.ndim != 1 or y.shape[0] != x.shape[0]:
-        raise ValueError(f"data y must have shape ({x.shape[0]},), got {y.shape}")
-    if x.shape[0] < 1:
-        raise ValueError("data needs at least one observation")
-    return x, y
-
-
-def _grouped_arrays(data, num_params: int):
-    """(x, y, group) of a grouped model (kUsesGroups) as contiguous arrays: x (num_obs, P) float64, y (num_obs,)
-    float64, group (num_obs,) int32, and J = num_params - P - 1 (the engine checks J >= 1, P >= 1 and the range)."""
-    x, y, group = data
-    x, y = _f64(x), _f64(y)
-    if x.ndim != 2:
-        raise ValueError(f"data x must have shape (num_obs, P), got {x.shape}")
-    if y.ndim != 1 or y.shape[0] != x.shape[0]:
-        raise ValueError(f"data y must have shape ({x.shape[0]},), got {y.shape}")
-    if x.shape[0] < 1:
-        raise ValueError("data needs at least one observation")
-    g = np.asarray(group)
-    if g.shape != y.shape:
-        raise ValueError(f"data group must have shape ({x.shape[0]},), got {g.shape}")
-    if g.dtype.kind not in "iu":
-        raise ValueError(f"data group must hold integers, got dtype {g.dtype}")
-    if g.size and (g.min() < np.iinfo(np.int32).min or g.max() > np.iinfo(np.int32).max):
-        raise ValueError("every group must be in [0, num_groups)")
-    return x, y, np.ascontiguousarray(g, dtype=np.int32), num_params - x.shape[1] - 1
-
-
-def _is_grouped(data) -> bool:
-    """data is an (x, y, group) triple rather than an (x, y) pair"""
-    try:
-        return len(data) == 3
-    except TypeError:
-        return False
-
-
-def _datasets_arrays(datasets, num_params: int, cols: Optional[int] = None):
-    """Several datasets [(x0, y0), (x1, y1), ...] as one block: x (rows, num_params) and y (rows,) stacked in order,
-    and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1]).  Triples (x, y, group) of a grouped
-    model give x (rows, P) and a fourth and fifth entry: the stacked int32 groups and J; pairs give None, 0 there."""
-    try:
-        items = list(datasets)
-    except TypeError:
-        raise ValueError("datasets must be a sequence of (x, y) pairs or (x, y, group) triples") from None
-    if not items:
-        raise ValueError("datasets needs at least one (x, y) pair")
-    grouped = _is_grouped(items[0])
-    if any(_is_grouped(d) != grouped for d in items):
-        raise ValueError("datasets must be all (x, y) pairs or all (x, y, group) triples")
-    if grouped:
-        parts = [_grouped_arrays(d, num_params) for d in items]
-        if len({p[0].shape[1] for p in parts}) != 1:
-            raise ValueError("every dataset's x must have the same number of columns")
-    else:
-        try:
-            parts = [_data_arrays(d, num_params if cols is None else cols) for d in items]
-        except TypeError:
-            raise ValueError("datasets must be a sequence of (x, y) pairs") from None
-    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum([p[1].size for p in parts])
-    x = np.ascontiguousarray(np.concatenate([p[0] for p in parts], axis=0))
-    y = np.ascontiguousarray(np.concatenate([p[1] for p in parts]))
-    if grouped:
-        return x, y, offsets, np.ascontiguousarray(np.concatenate([p[2] for p in parts])), parts[0][3]
-    return x, y, offsets, None, 0
-
-
 class DeviceEngine:
     def __init__(self, model: int, dim: int, num_chains: int, cfg: Optional[_ffi.Config] = None,
                  params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None, datasets=None):
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
         (num_obs, dim) and y of shape (num_obs,); copied to the device once.  `data=(x, y, group)` for a grouped model
         (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
-        [0, J) with J = dim - P - 1 (wn_engine_create_with_grouped_data).  A model with a scale parameter
+        [0, J) with J = dim - P - 1.  A model with a scale parameter
         (MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA) takes x of shape (num_obs, dim - 1): its last
         coordinate is s, not a column of x.  The count models (MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION,
         MODEL_HIER_POISSON_REGRESSION*) need every y to be a finite non-negative integer.
 
         `datasets=[(x0, y0), (x1, y1), ...]` instead: G datasets of the same model and prior (sizes may differ), fitted
-        side by side (wn_engine_create_with_datasets).  num_chains must be a multiple k of G; chains [g*k, (g+1)*k)
+        side by side (wn_observations::obs_offsets).  num_chains must be a multiple k of G; chains [g*k, (g+1)*k)
         are conditioned on dataset g and evolve exactly as chains 0..k-1 of an engine built with data=(xg, yg) and
         seeded with chain_offset = g*k.  Per-dataset statistics: rhat_per_dataset(), warmup_spread_per_dataset();
         init_masses_from_grad(average=True) averages over each dataset's chains.  A grouped model takes triples
-        [(x0, y0, g0), ...] with the same number of columns in every x (wn_engine_create_with_grouped_datasets)."""
-        if data is not None and datasets is not None:
-            raise ValueError("data and datasets are mutually exclusive")
+        [(x0, y0, g0), ...] with the same number of columns in every x."""
         self.lib = _ffi.load_library(lib_path)
         self.cfg = cfg if cfg is not None else default_config(lib_path)
         self.C, self.D = int(num_chains), int(dim)
@@ -173,29 +83,12 @@ class DeviceEngine:
         h, err = C.c_void_p(), C.c_void_p()
         pp = None if p is None else p.ctypes.data_as(_dp)
         self._several = datasets is not None
-        if datasets is not None:
-            x, y, off, grp, J = _datasets_arrays(datasets, self.D, _data_columns(self.lib, model, self.D))
-            if grp is not None:
-                rc = self.lib.wn_engine_create_with_grouped_datasets(
-                    C.byref(h), model, dim, pp, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp),
-                    grp.ctypes.data_as(_ffi._i32p), J, off.ctypes.data_as(_ffi._i64p), off.size - 1, num_chains,
-                    C.byref(self.cfg), C.byref(err))
-            else:
-                rc = self.lib.wn_engine_create_with_datasets(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
-                                                             y.ctypes.data_as(_dp), off.ctypes.data_as(_ffi._i64p),
-                                                             off.size - 1, num_chains, C.byref(self.cfg), C.byref(err))
-        elif data is None:
+        obs = observations(self.lib, model, self.D, data, datasets)
+        if obs is None:
             rc = self.lib.wn_engine_create(C.byref(h), model, dim, pp, num_chains, C.byref(self.cfg), C.byref(err))
-        elif _is_grouped(data):
-            x, y, grp, J = _grouped_arrays(data, self.D)
-            rc = self.lib.wn_engine_create_with_grouped_data(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
-                                                             y.ctypes.data_as(_dp), grp.ctypes.data_as(_ffi._i32p), J,
-                                                             y.size, num_chains, C.byref(self.cfg), C.byref(err))
         else:
-            x, y = _data_arrays(data, _data_columns(self.lib, model, self.D))
-            rc = self.lib.wn_engine_create_with_data(C.byref(h), model, dim, pp, x.ctypes.data_as(_dp),
-                                                     y.ctypes.data_as(_dp), y.size, num_chains, C.byref(self.cfg),
-                                                     C.byref(err))
+            rc = self.lib.wn_engine_create_observed(C.byref(h), model, dim, pp, C.byref(obs), num_chains,
+                                                    C.byref(self.cfg), C.byref(err))
         _ffi.check(self.lib, rc, err)
         self.h = h
 
