@@ -21,7 +21,8 @@
 //  * The "other" end of the accumulated span is one (theta, rho[, grad]) triple that is swapped with the moving
 //    end when the walk turns around; nothing is written while the walk keeps its direction.  For models whose
 //    gradient is recomputed it is parked in accumulator registers (AGPRs), which vector arithmetic cannot read and
-//    the register allocator therefore leaves alone.
+//    the register allocator therefore leaves alone.  The top-level U-turn test fetches it into set 1, where a
+//    turn-around of the next doubling finds it: turning around reads nothing back from the accumulator file.
 //  * The first doubling (a single leaf) is peeled out of the doubling loop: the two shapes share one generic lambda
 //    but not their register assignments -- in one loop the allocator re-homed whole vectors on every doubling.
 #pragma once
@@ -715,20 +716,18 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
       } else if (fwd != hot_fw) {
         // the walk turns around: the moving end and the parked end change places
         if (kOtherRegs) {
+          // The other end is also in set 1 (see "set 1 at a doubling's end" below): nothing is fetched back from the
+          // accumulator file -- the selection's copy and the new moving end are taken from set 1, set 0 is parked.
           if (a_sel == kOther) {  // the selected position was the other end's: it gets a buffer of its own
             a_sel = this->alloc_cold();
-            double t[EPL];
-#pragma unroll
-            for (int j = 0; j < EPL; ++j) t[j] = fetch(oth[j]);
-            pool_store(a_sel, t);
+            pool_store(a_sel, th[1]);
           }
 #pragma unroll
           for (int j = 0; j < EPL; ++j) {
-            const double t0 = th[0][j], t1 = rh[0][j];
-            th[0][j] = fetch(oth[j]);
-            rh[0][j] = fetch(orh[j]);
-            park(oth[j], t0);
-            park(orh[j], t1);
+            park(oth[j], th[0][j]);
+            park(orh[j], rh[0][j]);
+            th[0][j] = th[1][j];
+            rh[0][j] = rh[1][j];
           }
         } else {
           double a[EPL], b[EPL];
@@ -879,24 +878,8 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
 
       // ---- merge into the accumulated span (walnuts.hpp:546-548) ----
       WN_PHASE(kPhTopMerge);
-      bool turned;
-      if (kFirst) {
-        turned = top_turned;
-      } else {
-        if (kOtherRegs) {
-          double p_hot, p_far;
-          double a[EPL], b[EPL];
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) {
-            a[j] = fetch(oth[j]);
-            b[j] = fetch(orh[j]);
-          }
-          uturn_partials<0>(a, b, p_hot, p_far);
-          turned = turned_packed(p_hot, p_far, fwd);
-        } else {
-          turned = uturn_pool(o_th, o_rh, fwd);
-        }
-      }
+      bool turned = top_turned;
+      if (!kFirst && !kOtherRegs) turned = uturn_pool(o_th, o_rh, fwd);
       const bool update = this->uniform01_ready() * a_w < c_w;  // Metropolis
       // the new span's inner end is never read again
       this->release_unless(c_in_th, c_sel, -3, -3);
@@ -908,6 +891,21 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
         a_lpsel = c_lpsel;
       } else {
         this->release(c_sel);
+      }
+      // Set 1 at a doubling's end: the accumulated span's other end.  The first doubling leaves it there (the initial
+      // point its single leaf started from); a later one fetches the parked end INTO set 1 for the top-level U-turn test
+      // (walnuts.hpp:549) -- after the bookkeeping above, which may still have read the even leaf there (c_sel ==
+      // kStart), and which takes no draw the test could reorder.  A next doubling that turns around finds the operands
+      // of this test where it needs them; one that does not lets them die (the accumulator copy stays valid).
+      if (!kFirst && kOtherRegs) {
+        double p_hot, p_far;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) {
+          th[1][j] = fetch(oth[j]);
+          rh[1][j] = fetch(orh[j]);
+        }
+        uturn_partials<0>(th[1], rh[1], p_hot, p_far);
+        turned = turned_packed(p_hot, p_far, fwd);
       }
       lj_hot = h_cur;
       a_w = uni(a_w + c_w);
