@@ -157,7 +157,18 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
  * MANY datasets at once (one model, one prior): with obs_offsets != NULL, dataset g is rows [obs_offsets[g],
  * obs_offsets[g + 1]) of x, y and group (from 0, strictly increasing; datasets may differ in size; num_groups is shared
  * and a dataset may leave groups empty), and chain c is conditioned on dataset c / k, k = num_chains / num_datasets
- * (num_chains a multiple of num_datasets). */
+ * (num_chains a multiple of num_datasets).
+ * OFFSETS and WEIGHTS per row (models that declare kUsesRowTerms: every built-in data model), each optional, sliced by
+ * obs_offsets like y:  eta_n = x_n . beta (+ group effect) + offset_n,  logp = prior + sum_n weight_n ll_n,  the priors
+ * unweighted.  offset: exposure of a count model (log E), a known term of any linear predictor.  weight >= 0: frequency
+ * or importance weights; binomial counts (k successes in m trials: weight m, y = k / m -- on an engine WITH weights the
+ * logistic models take any y in [0, 1]).  A row of weight 0 contributes exactly nothing, whatever its eta; an all-zero
+ * vector leaves the prior.
+ * WEIGHT SETS (num_weight_sets = W > 1; not with obs_offsets): weight is [W][num_obs] over the ONE shared block x, y,
+ * offset, group, and chain c uses set c / k, k = num_chains / W (num_chains a multiple of W) -- K-fold refits, the
+ * bootstrap: the same rows under different weights, stored once.  Such an engine is one of W datasets for everything
+ * else: wn_engine_num_datasets, the _datasets monitors, the per-dataset stopping rules and output blocks below.
+ * New fields are appended and zero / NULL means absent. */
 typedef struct wn_observations {
   const double* x;            /* [rows][cols] row-major */
   const double* y;            /* [rows] */
@@ -166,6 +177,9 @@ typedef struct wn_observations {
   int num_groups;
   const int64_t* obs_offsets; /* [num_datasets + 1]; NULL: one block shared by every chain */
   int num_datasets;
+  const double* offset;       /* [rows]; NULL: none */
+  const double* weight;       /* [rows], or [num_weight_sets][num_obs]; NULL: every weight 1 */
+  int num_weight_sets;        /* 0 or 1: one weight vector; W > 1: weight sets */
 } wn_observations;
 
 /* walnutpie_sample_device / _resident for a model conditioned on data: `obs` after num_params, everything else as the
@@ -359,13 +373,15 @@ WALNUTS_HIP_EXPORT int wn_engine_create(wn_engine** out, int model, int num_para
  * per dataset.  `config` errors: obs == NULL; a data model created through wn_engine_create; data for a model without
  * kUsesData; a grouped model without `group`, and `group` for a model without kUsesGroups; num_params != P + num_groups
  * + 1 with P >= 1 and num_groups >= 1; num_datasets < 1, num_chains not a multiple of it, offsets not from 0 or not
- * strictly increasing; non-finite data; a group outside [0, num_groups); the model's own data checks failing (for a
- * dataset: the message names it); a data model outside one wavefront per chain (num_params > 1024, or an explicit wider
- * geometry). */
+ * strictly increasing; non-finite data; a group outside [0, num_groups); a non-finite offset; a weight that is negative
+ * or not finite; offsets or weights for a model without kUsesRowTerms; num_weight_sets < 0, > 1 without `weight`, > 1
+ * together with obs_offsets, or not dividing num_chains (all checked before anything is uploaded); the model's own
+ * data checks failing (for a dataset: the message names it); a data model outside one wavefront per chain (num_params >
+ * 1024, or an explicit wider geometry). */
 WALNUTS_HIP_EXPORT int wn_engine_create_observed(wn_engine** out, int model, int num_params, const double* model_params,
                                                  const wn_observations* obs, size_t num_chains, const wn_config* cfg,
                                                  WalnutpyError** err);
-/* datasets of an engine (1 for one created without obs_offsets) */
+/* datasets of an engine (1 for one created without obs_offsets; num_weight_sets for one created with weight sets) */
 WALNUTS_HIP_EXPORT int wn_engine_num_datasets(const wn_engine* e);
 WALNUTS_HIP_EXPORT void wn_engine_destroy(wn_engine* e);
 /* The engine's model at positions the caller chooses: theta [C*D] in, logp_out [C] and grad_out [C*D] out (host

@@ -56,6 +56,9 @@ class Observations(C.Structure):
         ("num_groups", C.c_int),
         ("obs_offsets", _i64p),
         ("num_datasets", C.c_int),
+        ("offset", _dp),
+        ("weight", _dp),
+        ("num_weight_sets", C.c_int),
     ]
 
 

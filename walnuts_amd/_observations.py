@@ -80,13 +80,50 @@ def _blocks(datasets, num_params: int, cols: int):
     return x, y, group, parts[0][3], offsets
 
 
-def observations(lib, model: int, num_params: int, data=None, datasets=None):
-    """The wn_observations of `data=(x, y[, group])` or `datasets=[(x0, y0[, group0]), ...]`, or None without either.
-    The struct keeps the arrays it points into alive (`.arrays`); pass it with ctypes.byref."""
+def _row_terms(name: str, value, sizes, several: bool):
+    """`offset=` / `weights=` as one float64 array over all rows, or None.  With `data=`: an array of shape (num_obs,).
+    With `datasets=`: a sequence with one entry per dataset, each an array of that dataset's (num_obs,) or None (offset
+    0 / weight 1 there); all None gives None."""
+    if value is None:
+        return None
+    fill = 1.0 if name == "weights" else 0.0
+    if not several:
+        a = _f64(value)
+        if a.shape != (sizes[0],):
+            raise ValueError(f"{name} must have shape ({sizes[0]},), got {a.shape}")
+        return a
+    try:
+        items = list(value)
+    except TypeError:
+        raise ValueError(f"{name} must be a sequence with one array (or None) per dataset") from None
+    if len(items) != len(sizes):
+        raise ValueError(f"{name} must have one entry per dataset ({len(sizes)}), got {len(items)}")
+    if all(v is None for v in items):
+        return None
+    parts = []
+    for g, (v, n) in enumerate(zip(items, sizes)):
+        a = np.full(n, fill) if v is None else _f64(v)
+        if a.shape != (n,):
+            raise ValueError(f"{name} of dataset {g} must have shape ({n},), got {a.shape}")
+        parts.append(a)
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+def observations(lib, model: int, num_params: int, data=None, datasets=None, offset=None, weights=None,
+                 weight_sets=None):
+    """The wn_observations of `data=(x, y[, group])` or `datasets=[(x0, y0[, group0]), ...]`, or None without either,
+    with the per-row `offset=` and `weights=` (one array, or one per dataset) and `weight_sets=` ((W, num_obs), with
+    `data=` only).  The struct keeps the arrays it points into alive (`.arrays`); pass it with ctypes.byref."""
     if data is not None and datasets is not None:
         raise ValueError("data and datasets are mutually exclusive")
     if data is None and datasets is None:
+        if offset is not None or weights is not None or weight_sets is not None:
+            raise ValueError("offset, weights and weight_sets need data or datasets")
         return None
+    if weight_sets is not None and datasets is not None:
+        raise ValueError("weight_sets is available with data only (the sets share one block of rows)")
+    if weight_sets is not None and weights is not None:
+        raise ValueError("weights and weight_sets are mutually exclusive")
     # columns of x of a flat data model (wn_model_data_columns): num_params, or num_params - 1 for a model with a scale
     # parameter.  An id that holds no flat data model gives num_params, and the engine then refuses the model (or the
     # pair (x, y) for a grouped model) with its own message.
@@ -103,5 +140,17 @@ def observations(lib, model: int, num_params: int, data=None, datasets=None):
     obs.x, obs.y = x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp)
     if group is not None:
         obs.group, obs.num_groups = group.ctypes.data_as(_ffi._i32p), J
-    obs.arrays = (x, y, group, offsets)
+    sizes = [y.size] if offsets is None else list(np.diff(offsets))
+    off = _row_terms("offset", offset, sizes, offsets is not None)
+    wts = _row_terms("weights", weights, sizes, offsets is not None)
+    if weight_sets is not None:
+        wts = _f64(weight_sets)
+        if wts.ndim != 2 or wts.shape[1] != y.size or wts.shape[0] < 1:
+            raise ValueError(f"weight_sets must have shape (W, {y.size}), got {wts.shape}")
+        obs.num_weight_sets = wts.shape[0]
+    if off is not None:
+        obs.offset = off.ctypes.data_as(_ffi._dp)
+    if wts is not None:
+        obs.weight = wts.ctypes.data_as(_ffi._dp)
+    obs.arrays = (x, y, group, offsets, off, wts)
     return obs

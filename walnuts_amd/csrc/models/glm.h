@@ -26,6 +26,18 @@
 // partial block reads no row at or beyond num_obs: its missing rows are zeros and their residuals and terms are
 // masked to 0.  The CPU emulation runs the same source with the same butterfly order, so the bits agree.
 //
+// Per-row offsets o_n and weights w_n >= 0 (kUsesRowTerms; either may be absent, a wave-uniform test per evaluation):
+//   eta_n = x_n . theta + o_n,   logp = prior + sum_n w_n ll_n(eta_n, y_n),   r_n = w_n d ll_n / d eta_n
+// in this order, shared by every data model (glm_scale.h, hier_glm.h):
+//   offset: between steps 1 and 2, lanes 0..B-1 add their row's o_n to eta (one add per block; lanes without a row add
+//           0.0) -- in hier_glm.h after the group effect was added;
+//   weight: the link is evaluated with a ZERO running sum, t = Link::term(eta, y, r, 0.0), then
+//           ll = Cx::mad(w, t, ll) and r = w * r (glm_scale.h: also ds = ds + w * ds_n, ds_n the row's own partial);
+//   w_n == 0: the row is discarded by SELECT, exactly as a row at or beyond num_obs (ll unchanged, r = 0), so it adds
+//           nothing even when its eta overflows the link (t, r inf or NaN).
+// Without weights the link receives the running sum as before and without offsets no add is issued: such an engine
+// computes what it computed before these fields existed, bit for bit.
+//
 // Arithmetic: the prior variances arrive as reciprocals (host_params, as the diagonal normal's); the logistic mean is
 // one true division per block-row evaluation, 1 / (1 + exp(-|eta|)), and softplus(eta) = max(eta, 0) +
 // log(1 + exp(-|eta|)) never overflows.  exp / log are wnd::dexp / wnd::dlog with per-lane arguments (gather tables).
@@ -46,7 +58,7 @@ struct IdentityLink {
     r = y - eta;
     return Cx::mad(-0.5 * r, r, ll);
   }
-  static void check_y(double) {}
+  static void check_y(double, bool) {}
 };
 
 struct LogitLink {
@@ -61,8 +73,14 @@ struct LogitLink {
     r = y - mu;
     return Cx::mad(y, eta, ll) - sp;
   }
-  static void check_y(double y) {
-    if (!(y == 0.0 || y == 1.0)) throw std::invalid_argument("logistic_regression needs every y in {0, 1}");
+  // (with weights y may be a proportion: k successes in m trials are weight m and y = k / m)
+  static void check_y(double y, bool weighted) {
+    if (weighted) {
+      if (!(y >= 0.0 && y <= 1.0))
+        throw std::invalid_argument("logistic_regression with weights needs every y in [0, 1], got " + std::to_string(y));
+    } else if (!(y == 0.0 || y == 1.0)) {
+      throw std::invalid_argument("logistic_regression needs every y in {0, 1}");
+    }
   }
 };
 
@@ -75,7 +93,7 @@ struct LogLink {
     r = y - mu;
     return Cx::mad(y, eta, ll) - mu;
   }
-  static void check_y(double y) { check_count(y, "Poisson regression"); }
+  static void check_y(double y, bool) { check_count(y, "Poisson regression"); }
   // a count: finite, >= 0 and integer-valued
   static void check_count(double y, const char* model) {
     if (!(std::isfinite(y) && y >= 0.0 && y == std::floor(y)))
@@ -83,6 +101,15 @@ struct LogLink {
                                   std::to_string(y));
   }
 };
+
+// The weighted form of a block's link results (header comment): t, r are the link's with a zero running sum; lanes
+// without a row hold w = 0.  -> the lane's running sum; r becomes the weighted residual.
+template <class Cx>
+__device__ __forceinline__ double weigh_row(double w, double t, double& r, double ll) {
+  const bool live = w != 0.0;
+  r = live ? w * r : 0.0;
+  return live ? Cx::mad(w, t, ll) : ll;
+}
 
 // the value of coordinate c (wave-uniform) of a vector laid out like theta, in every lane (one wavefront)
 template <int EPL>
@@ -98,6 +125,7 @@ template <class Link>
 struct GlmModel {
   static constexpr bool kUsesParams = true;  // prior variances s^2 [num_params]
   static constexpr bool kUsesData = true;
+  static constexpr bool kUsesRowTerms = true;
   static constexpr bool kElementwise = false;
   static constexpr bool kGradIsNegTheta = false;
   static constexpr bool kCheapGrad = false;
@@ -120,6 +148,7 @@ struct GlmModel {
     }
     const int N = cx.num_obs();
     const int me = opaque_lane_id();
+    const bool offs = cx.has_offset(), wts = cx.has_weight();
     double ll = 0.0;  // this lane's log-likelihood terms
     for (int n0 = 0; n0 < N; n0 += B) {
       double x[B][EPL];
@@ -147,10 +176,15 @@ struct GlmModel {
       }
       const bool mine = me < B && n0 + me < N;
       const double y = mine ? cx.obs_y(n0 + me) : 0.0;
+      if (offs) eta = eta + (mine ? cx.obs_offset(n0 + me) : 0.0);
       double r;
-      const double ll_new = Link::template term<Cx>(eta, y, r, ll, cx.gather_tab());
-      ll = mine ? ll_new : ll;
-      r = mine ? r : 0.0;
+      const double ll_new = Link::template term<Cx>(eta, y, r, wts ? 0.0 : ll, cx.gather_tab());
+      if (wts) {
+        ll = weigh_row<Cx>(mine ? cx.obs_weight(n0 + me) : 0.0, ll_new, r, ll);
+      } else {
+        ll = mine ? ll_new : ll;
+        r = mine ? r : 0.0;
+      }
 #pragma unroll
       for (int k = 0; k < B; ++k) {
         const double rk = lane_value(r, k);
@@ -169,8 +203,8 @@ struct GlmModel {
       s2[i] = 1.0 / s2[i];
     }
   }
-  static void host_data(const double*, const double* y, int num_obs, int) {
-    for (int n = 0; n < num_obs; ++n) Link::check_y(y[n]);
+  static void host_data(const double*, const double* y, int num_obs, int, bool weighted) {
+    for (int n = 0; n < num_obs; ++n) Link::check_y(y[n], weighted);
   }
   static void validate(int num_params) {
     if (num_params > 1024)

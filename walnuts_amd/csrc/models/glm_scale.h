@@ -20,6 +20,10 @@
 // phi and the lgamma / digamma constants of phi (wnd::GammaConsts), 1 / sigma^2 -- is computed once per evaluation from
 // the wave-uniform s.  A non-finite scale (s beyond about +-709) takes no path of its own: the energy turns non-finite
 // and the trajectory treats it as every non-finite energy.
+//
+// Per-row offsets and weights as in glm.h (its header states the order).  With weights the family's term is evaluated
+// with zero running sums (t, r, ds_n the row's own), then ds = ds + w * ds_n (a rounded product, then the add),
+// ll = Cx::mad(w, t, ll) and r = w * r; a row with w == 0 is discarded by select.
 #pragma once
 
 #include "glm.h"
@@ -53,7 +57,7 @@ struct NegBinomialFamily {
     ll = (ll + (Cx::mad(y, t, lg))) - yp * sp;
     ds = ds + Cx::mad(k.phi, sp - dg, r);
   }
-  static void check_y(double y) { LogLink::check_count(y, "negative binomial regression"); }
+  static void check_y(double y, bool) { LogLink::check_count(y, "negative binomial regression"); }
 };
 
 struct NormalSigmaFamily {
@@ -73,7 +77,7 @@ struct NormalSigmaFamily {
     ll = Cx::mad(-0.5 * d, r, ll) - k.s;
     ds = Cx::mad(d, r, ds) - 1.0;
   }
-  static void check_y(double) {}
+  static void check_y(double, bool) {}
 };
 
 template <class Family>
@@ -81,6 +85,7 @@ struct GlmScaleModel {
   static constexpr bool kUsesParams = true;  // [s2_0 .. s2_{P-1} | sigma_0]
   static constexpr bool kUsesData = true;
   static constexpr bool kScaleParam = true;
+  static constexpr bool kUsesRowTerms = true;
   static constexpr bool kElementwise = false;
   static constexpr bool kGradIsNegTheta = false;
   static constexpr bool kCheapGrad = false;
@@ -110,6 +115,7 @@ struct GlmScaleModel {
     }
     const int N = cx.num_obs();
     const int me = opaque_lane_id();
+    const bool offs = cx.has_offset(), wts = cx.has_weight();
     double ll = 0.0;  // this lane's log-likelihood terms
     double ds = 0.0;  // ... and their derivatives with respect to s
     for (int n0 = 0; n0 < N; n0 += B) {
@@ -138,11 +144,18 @@ struct GlmScaleModel {
       }
       const bool mine = me < B && n0 + me < N;
       const double y = mine ? cx.obs_y(n0 + me) : 0.0;
-      double r, ll_new = ll, ds_new = ds;
+      if (offs) eta = eta + (mine ? cx.obs_offset(n0 + me) : 0.0);
+      double r, ll_new = wts ? 0.0 : ll, ds_new = wts ? 0.0 : ds;
       Family::template term<Cx>(eta, y, k, cx.gather_tab(), r, ll_new, ds_new);
-      ll = mine ? ll_new : ll;
-      ds = mine ? ds_new : ds;
-      r = mine ? r : 0.0;
+      if (wts) {
+        const double w = mine ? cx.obs_weight(n0 + me) : 0.0;
+        ds = w != 0.0 ? ds + w * ds_new : ds;
+        ll = weigh_row<Cx>(w, ll_new, r, ll);
+      } else {
+        ll = mine ? ll_new : ll;
+        ds = mine ? ds_new : ds;
+        r = mine ? r : 0.0;
+      }
 #pragma unroll
       for (int kk = 0; kk < B; ++kk) {
         const double rk = lane_value(r, kk);
@@ -173,8 +186,8 @@ struct GlmScaleModel {
     for (int i = 0; i + 1 < num_params; ++i) mp[i] = 1.0 / mp[i];
     mp[num_params - 1] = 1.0 / (mp[num_params - 1] * mp[num_params - 1]);
   }
-  static void host_data(const double*, const double* y, int num_obs, int) {
-    for (int n = 0; n < num_obs; ++n) Family::check_y(y[n]);
+  static void host_data(const double*, const double* y, int num_obs, int, bool weighted) {
+    for (int n = 0; n < num_obs; ++n) Family::check_y(y[n], weighted);
   }
   static void validate(int num_params) {
     if (num_params < 2 || num_params > 1024)

@@ -24,6 +24,8 @@
 //   2. the residual of row k, broadcast for the gradient of beta, is added into S_g in the owner lane's slot of
 //      coordinate P + g (S_j accumulates in g[] there), rows in order: no atomics, no scheduling-dependent order, so
 //      the CPU emulation of the same source gives the same bits.
+// Per-row offsets and weights as in glm.h (its header states the order): the offset is added to eta after the group
+// effect; the residual carries the weight, so S_g is a weighted sum with no further code.
 // tau = wnd::dexp(s) of the wave-uniform s, once per evaluation; the epilogue applies the formulas above with one
 // cx.sum1 (sum_j z_j S_j, or sum_j a_j^2).  A non-finite tau (s beyond +-709) takes no path of its own: the energy
 // turns non-finite and the trajectory treats it as every non-finite energy.
@@ -38,6 +40,7 @@ struct HierGlmModel {
   static constexpr bool kUsesParams = true;  // [s2_0 .. s2_{P-1} | 1 .. 1 | sigma_tau]
   static constexpr bool kUsesData = true;
   static constexpr bool kUsesGroups = true;
+  static constexpr bool kUsesRowTerms = true;
   static constexpr bool kElementwise = false;
   static constexpr bool kGradIsNegTheta = false;
   static constexpr bool kCheapGrad = false;
@@ -79,6 +82,7 @@ struct HierGlmModel {
     }
     const int N = cx.num_obs();
     const int me = opaque_lane_id();
+    const bool offs = cx.has_offset(), wts = cx.has_weight();
     double ll = 0.0;  // this lane's log-likelihood terms
     for (int n0 = 0; n0 < N; n0 += B) {
       double x[B][EPL];
@@ -118,10 +122,15 @@ struct HierGlmModel {
       }
       eta = eta + v;
       const double y = mine ? cx.obs_y(n0 + me) : 0.0;
+      if (offs) eta = eta + (mine ? cx.obs_offset(n0 + me) : 0.0);
       double r;
-      const double ll_new = Link::template term<Cx>(eta, y, r, ll, cx.gather_tab());
-      ll = mine ? ll_new : ll;
-      r = mine ? r : 0.0;
+      const double ll_new = Link::template term<Cx>(eta, y, r, wts ? 0.0 : ll, cx.gather_tab());
+      if (wts) {
+        ll = weigh_row<Cx>(mine ? cx.obs_weight(n0 + me) : 0.0, ll_new, r, ll);
+      } else {
+        ll = mine ? ll_new : ll;
+        r = mine ? r : 0.0;
+      }
 #pragma unroll
       for (int k = 0; k < B; ++k) {
         const double rk = lane_value(r, k);
@@ -177,8 +186,8 @@ struct HierGlmModel {
     for (int i = 0; i + 1 < num_params; ++i) mp[i] = 1.0 / mp[i];
     mp[num_params - 1] = 1.0 / (mp[num_params - 1] * mp[num_params - 1]);
   }
-  static void host_data(const double*, const double* y, int num_obs, int) {
-    for (int n = 0; n < num_obs; ++n) Link::check_y(y[n]);
+  static void host_data(const double*, const double* y, int num_obs, int, bool weighted) {
+    for (int n = 0; n < num_obs; ++n) Link::check_y(y[n], weighted);
   }
   static void validate(int num_params) {
     if (num_params > 1024)

@@ -99,6 +99,8 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   const double* obs_x = nullptr;              // data models: the bound chain's observations (bind_data)
   const double* obs_yv = nullptr;
   const int32_t* obs_gv = nullptr;            // grouped data models: the bound chain's group indices
+  const double* obs_ov = nullptr;             // kUsesRowTerms: the bound chain's offsets and weights (null: absent)
+  const double* obs_wv = nullptr;
   int obs_n = 0;
   int shift_parity = 0;                       // which copy of the shift scratch the last exchange used
 #if defined(WN_COUNT_POOL)
@@ -150,23 +152,49 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   // grouped data models (kUsesGroups): J, wave-uniform, and the group of observation n, in [0, J)
   __device__ __forceinline__ int num_groups() const { return P.obs.num_groups; }
   __device__ __forceinline__ int obs_group(int n) const { return obs_gv[n]; }
+  // data models that read per-row offsets and weights (kUsesRowTerms): whether the engine holds them (wave-uniform),
+  // and observation n's (only where has_*() is true)
+  __device__ __forceinline__ bool has_offset() const { return obs_ov != nullptr; }
+  __device__ __forceinline__ bool has_weight() const { return obs_wv != nullptr; }
+  __device__ __forceinline__ double obs_offset(int n) const { return obs_ov[n]; }
+  __device__ __forceinline__ double obs_weight(int n) const { return obs_wv[n]; }
   // Once per chain, before the model is evaluated for it: chain c of an engine with several datasets reads dataset
   // c / chains_per_dataset (the chain index is wave-uniform: one division and two scalar loads per chain, none per
-  // row).  Row offsets are 64-bit, so a block beyond 4 GiB is addressed correctly.
+  // row).  Row offsets are 64-bit, so a block beyond 4 GiB is addressed correctly.  With WEIGHT SETS
+  // (chains_per_dataset > 0 and no offsets array) x, y, offset and group are bound whole and the quotient selects the
+  // chain's weight vector.
   __device__ __forceinline__ void bind_data(int c) {
     if constexpr (uses_data<Model>::value) {
-      if (P.obs.chains_per_dataset > 0) {
+      if (P.obs.chains_per_dataset > 0 && P.obs.offsets == nullptr) {
+        obs_x = P.obs.x;
+        obs_yv = P.obs.y;
+        if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group;
+        obs_n = P.obs.num_obs;
+        if constexpr (uses_row_terms<Model>::value) {
+          const int set = c / P.obs.chains_per_dataset;
+          obs_ov = P.obs.offset;
+          obs_wv = P.obs.weight + static_cast<long long>(set) * P.obs.num_obs;
+        }
+      } else if (P.obs.chains_per_dataset > 0) {
         const int ds = c / P.obs.chains_per_dataset;
         const long long first = P.obs.offsets[ds];
         obs_x = P.obs.x + first * (uses_groups<Model>::value ? static_cast<long long>(P.obs.stride) : kDp);
         obs_yv = P.obs.y + first;
         if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group + first;
         obs_n = static_cast<int>(P.obs.offsets[ds + 1] - first);
+        if constexpr (uses_row_terms<Model>::value) {
+          obs_ov = P.obs.offset != nullptr ? P.obs.offset + first : nullptr;
+          obs_wv = P.obs.weight != nullptr ? P.obs.weight + first : nullptr;
+        }
       } else {
         obs_x = P.obs.x;
         obs_yv = P.obs.y;
         if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group;
         obs_n = P.obs.num_obs;
+        if constexpr (uses_row_terms<Model>::value) {
+          obs_ov = P.obs.offset;
+          obs_wv = P.obs.weight;
+        }
       }
     }
   }

@@ -85,9 +85,10 @@ struct wn_engine {
   // a data model's observations, as the kernels take them (wn_params.h), and the buffers `obs` points into: x
   // [rows][obs.stride] (rows padded with zeros), y [rows]; with several datasets one after another, dataset g being rows
   // [offsets[g], offsets[g + 1]) and chains [g * k, (g + 1) * k), k = obs.chains_per_dataset; a grouped model's group
-  // of every row, its x (P = D - J - 1 columns) at the narrower stride 128 * ceil(P / 128)
+  // of every row, its x (P = D - J - 1 columns) at the narrower stride 128 * ceil(P / 128); optional offsets and weights
+  // of every row, or weight sets: one block of rows, num_datasets weight vectors, k chains each
   wn::Observations obs{};
-  DevBuf<double> data_x, data_y;
+  DevBuf<double> data_x, data_y, data_offset, data_weight;  // (weight: [num_datasets][num_obs] with weight sets)
   DevBuf<int64_t> data_offsets;
   DevBuf<int32_t> data_group;
   int num_datasets = 1;
@@ -467,6 +468,22 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
                                 "[num_obs] in [0, num_groups))");
   if (!ops.uses_groups && data != nullptr && data->group != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
+  if (!ops.uses_row_terms && data != nullptr && (data->offset != nullptr || data->weight != nullptr))
+    throw std::invalid_argument(std::string(ops.name) + " model reads no offsets or weights (it does not declare "
+                                "kUsesRowTerms)");
+  // weight sets: W weight vectors over the one shared block, an engine of W datasets for everything above the kernels
+  const int weight_sets = data != nullptr && data->num_weight_sets > 1 ? data->num_weight_sets : 1;
+  if (data != nullptr) {
+    if (data->num_weight_sets < 0) throw std::invalid_argument("num_weight_sets must not be negative");
+    if (weight_sets > 1 && data->weight == nullptr)
+      throw std::invalid_argument("num_weight_sets > 1 needs weight [num_weight_sets][num_obs]");
+    if (weight_sets > 1 && data->obs_offsets != nullptr)
+      throw std::invalid_argument("weight sets share one block of rows: not with obs_offsets (several datasets)");
+    if (weight_sets > 1 && num_chains % static_cast<size_t>(weight_sets) != 0)
+      throw std::invalid_argument("num_chains must be a multiple of num_weight_sets (chain c reads weight set c / "
+                                  "(num_chains / num_weight_sets))");
+  }
+  const bool weighted = data != nullptr && data->weight != nullptr;
   // columns of x: num_params, num_params - 1 for a model with a scale parameter, or P = num_params - J - 1 for a
   // grouped model
   int cols = ops.scale_param ? num_params - 1 : num_params;
@@ -508,14 +525,27 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
         if (data->group[i] < 0 || data->group[i] >= data->num_groups)
           throw std::invalid_argument("every group must be in [0, num_groups), observation " + std::to_string(i) + " has " +
                                       std::to_string(data->group[i]));
+    if (data->offset != nullptr)
+      for (size_t i = 0; i < total_obs; ++i)
+        if (!std::isfinite(data->offset[i]))
+          throw std::invalid_argument("every offset must be finite, observation " + std::to_string(i) + " has " +
+                                      std::to_string(data->offset[i]));
+    if (weighted) {
+      const size_t nw = total_obs * static_cast<size_t>(weight_sets);
+      for (size_t i = 0; i < nw; ++i)
+        if (!(data->weight[i] >= 0.0) || !std::isfinite(data->weight[i]))
+          throw std::invalid_argument("every weight must be finite and >= 0, observation " + std::to_string(i % total_obs) +
+                                      (weight_sets > 1 ? " of weight set " + std::to_string(i / total_obs) : std::string()) +
+                                      " has " + std::to_string(data->weight[i]));
+    }
     if (data->obs_offsets == nullptr) {
-      ops.host_data(data->x, data->y, data->num_obs, cols);
+      ops.host_data(data->x, data->y, data->num_obs, cols, weighted);
     } else {
       for (int g = 0; g < data->num_datasets; ++g) {
         const int64_t first = data->obs_offsets[g];
         try {
           ops.host_data(data->x + static_cast<size_t>(first) * cols, data->y + first,
-                        static_cast<int>(data->obs_offsets[g + 1] - first), cols);
+                        static_cast<int>(data->obs_offsets[g + 1] - first), cols, weighted);
         } catch (const std::invalid_argument& ex) {
           throw std::invalid_argument("dataset " + std::to_string(g) + ": " + ex.what());
         }
@@ -692,7 +722,24 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
       e.obs.group = e.data_group.p;
       e.obs.num_groups = data->num_groups;
     }
-    if (data->obs_offsets != nullptr) {
+    if (data->offset != nullptr) {
+      e.data_offset.alloc(N);
+      HIP_OK(hipMemcpyAsync(e.data_offset.p, data->offset, N * sizeof(double), hipMemcpyHostToDevice, e.stream));
+      e.obs.offset = e.data_offset.p;
+    }
+    if (weighted) {
+      const size_t nw = N * static_cast<size_t>(weight_sets);
+      e.data_weight.alloc(nw);
+      HIP_OK(hipMemcpyAsync(e.data_weight.p, data->weight, nw * sizeof(double), hipMemcpyHostToDevice, e.stream));
+      e.obs.weight = e.data_weight.p;
+    }
+    if (weight_sets > 1) {
+      // the rows are shared and the kernels take set c / k of the weights (bind_data: chains_per_dataset > 0 without
+      // an offsets array); above the kernels the sets are the engine's datasets
+      e.obs.num_obs = data->num_obs;
+      e.obs.chains_per_dataset = static_cast<int>(num_chains / static_cast<size_t>(weight_sets));
+      e.num_datasets = weight_sets;
+    } else if (data->obs_offsets != nullptr) {
       // the datasets one after another; the kernels take every chain's row count from the offsets (obs.num_obs = 0)
       const size_t G = static_cast<size_t>(data->num_datasets);
       e.data_offsets.alloc(G + 1);
@@ -1327,7 +1374,7 @@ void average_masses_segments(wn_engine& e, int G, int k) {
 
 void require_datasets(const wn_engine* e) {
   if (e->obs.chains_per_dataset == 0)
-    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_observed with obs_offsets)");
+    throw std::invalid_argument("this engine holds no datasets (wn_engine_create_observed with obs_offsets or weight sets)");
 }
 }  // namespace
 

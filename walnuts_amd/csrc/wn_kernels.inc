@@ -22,6 +22,7 @@ static constexpr bool kUsesData = uses_data<WN_MODEL_TYPE>::value;
 static_assert(!(kUsesData && kHasStreaming), "a data model has no streaming form (wn_model_api.h)");
 static_assert(!uses_groups<WN_MODEL_TYPE>::value || kUsesData, "kUsesGroups needs kUsesData (wn_model_api.h)");
 static_assert(!scale_param<WN_MODEL_TYPE>::value || kUsesData, "kScaleParam needs kUsesData (wn_model_api.h)");
+static_assert(!uses_row_terms<WN_MODEL_TYPE>::value || kUsesData, "kUsesRowTerms needs kUsesData (wn_model_api.h)");
 static_assert(!(scale_param<WN_MODEL_TYPE>::value && uses_groups<WN_MODEL_TYPE>::value),
               "kScaleParam and kUsesGroups do not combine (wn_model_api.h)");
 static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }
@@ -218,14 +219,21 @@ int WN_CAT(hold_tiles_, WN_MODEL_TAG)(int nw) {
 }
 void WN_CAT(host_params_, WN_MODEL_TAG)(double* p, int n) { call_host_params<WN_MODEL_TYPE>(p, n, 0); }
 void WN_CAT(validate_, WN_MODEL_TAG)(int n) { call_validate<WN_MODEL_TYPE>(n, 0); }
+// (a model whose checks depend on whether the engine carries weights takes the flag as a fifth argument)
 template <class M>
-auto call_host_data(const double* x, const double* y, int n, int d, int) -> decltype(M::host_data(x, y, n, d), void()) {
+auto call_host_data(const double* x, const double* y, int n, int d, bool w, int, int)
+    -> decltype(M::host_data(x, y, n, d, w), void()) {
+  M::host_data(x, y, n, d, w);
+}
+template <class M>
+auto call_host_data(const double* x, const double* y, int n, int d, bool, int, long)
+    -> decltype(M::host_data(x, y, n, d), void()) {
   M::host_data(x, y, n, d);
 }
 template <class M>
-void call_host_data(const double*, const double*, int, int, long) {}
-void WN_CAT(host_data_, WN_MODEL_TAG)(const double* x, const double* y, int n, int d) {
-  call_host_data<WN_MODEL_TYPE>(x, y, n, d, 0);
+void call_host_data(const double*, const double*, int, int, bool, long, long) {}
+void WN_CAT(host_data_, WN_MODEL_TAG)(const double* x, const double* y, int n, int d, bool weighted) {
+  call_host_data<WN_MODEL_TYPE>(x, y, n, d, weighted, 0, 0);
 }
 }  // namespace
 
@@ -249,7 +257,8 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     &WN_CAT(launch_eval_, WN_MODEL_TAG),
     &WN_CAT(host_data_, WN_MODEL_TAG),
     uses_groups<WN_MODEL_TYPE>::value,
-    scale_param<WN_MODEL_TYPE>::value};
+    scale_param<WN_MODEL_TYPE>::value,
+    uses_row_terms<WN_MODEL_TYPE>::value};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

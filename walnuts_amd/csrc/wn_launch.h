@@ -185,10 +185,12 @@ struct ModelOps {
   bool uses_data;             // reads an observation block (kUsesData): one wavefront per chain, register kernels only
   // the model's log density and gradient at given positions (eval_kernel, wn_init.h: wn_engine_eval)
   void (*launch_eval)(const Geometry&, int grid, size_t smem, hipStream_t, bool fma, const InitParams&);
-  // data models: validate the observations before upload (x [num_obs][num_params] row-major, y [num_obs])
-  void (*host_data)(const double* x, const double* y, int num_obs, int num_params);
+  // data models: validate the observations before upload (x [num_obs][num_params] row-major, y [num_obs]; weighted:
+  // the engine carries per-row weights, so a y that stands for a proportion is admissible)
+  void (*host_data)(const double* x, const double* y, int num_obs, int num_params, bool weighted);
   bool uses_groups;  // a data model that reads a group index per observation (kUsesGroups)
   bool scale_param;  // a flat data model whose last coordinate is a scale parameter, not a column of x (kScaleParam)
+  bool uses_row_terms;  // a data model that reads per-row offsets and weights (kUsesRowTerms)
 };
 constexpr int kMaxModels = 64;
 inline const ModelOps** model_table() {
@@ -203,7 +205,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 12;
+constexpr int kModelAbiVersion = 13;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

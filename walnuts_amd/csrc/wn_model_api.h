@@ -61,6 +61,8 @@
 //     // geometries, a data model without data and data for a model without this member (`config` errors).
 //     static constexpr bool kUsesData = true;
 //     static void host_data(const double* x, const double* y, int num_obs, int num_params);  // optional checks (throw)
+//     // (... or with a fifth argument `bool weighted`: whether the engine carries per-row weights, for a model whose
+//     // admissible y depends on it -- logistic_regression then takes proportions in [0, 1])
 //     // ... and, on top of kUsesData, a GROUP per observation (int32 in [0, J), copied beside y; wn_observations::group,
 //     // num_groups): x then has P = num_params - J - 1 columns, stored at the narrower row stride
 //     // Dx = 128 * ceil(P / 128) (host_data's last argument is P).
@@ -70,6 +72,11 @@
 //     // coordinate: x has P = num_params - 1 columns, stored at the flat stride Dp with column num_params - 1 zero, so
 //     // the row pass never sees the scale (host_data's last argument is P).  models/glm_scale.h.
 //     static constexpr bool kScaleParam = true;
+//     // ... and, on top of kUsesData, per-row OFFSETS and WEIGHTS (wn_observations::offset / weight /
+//     // num_weight_sets; each optional at run time): the model reads them through cx.has_offset() / obs_offset() /
+//     // has_weight() / obs_weight() below.  wn_engine_create refuses offsets or weights for a model without this member,
+//     // and a model without it compiles nothing of them.
+//     static constexpr bool kUsesRowTerms = true;
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -95,6 +102,12 @@
 //   cx.obs_group(n)                           the group of observation n, in [0, J) (0 <= n < num_obs)
 //   (cx.load_row then fills slot pairs k < Dx / 128 -- columns [128 k, 128 k + 128) -- and zeros the rest without
 //   loading them; a flat model's rows keep the stride Dp and its loads)
+// ... and for data models that declare kUsesRowTerms (eta_n += offset_n; the row's likelihood term and residual times
+// weight_n >= 0; models/glm.h states the order of operations every built-in model follows):
+//   cx.has_offset(), cx.has_weight()          whether the engine holds offsets / weights, wave-uniform: test once per
+//                                             evaluation or per block, never per element
+//   cx.obs_offset(n), cx.obs_weight(n)        offset_n / weight_n (0 <= n < num_obs; only where has_*() is true) -- with
+//                                             weight sets, of the set the chain is conditioned on; the model cannot tell
 // The wavefront primitives of the platform layer (wave_sum_packed, lane_value, set_lane, uni, ...: wn_gfx950.h, with
 // the same association order under the CPU emulation) are available to eval(); models/glm.h uses them to reduce two
 // rows' dot products per butterfly.

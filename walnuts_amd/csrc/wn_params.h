@@ -24,7 +24,7 @@ enum ModelKind : int32_t { kStdNormal = 0, kDiagNormal = 1, kFunnel = 2 };
 enum RngMode : int32_t { kRngPhilox = 0, kRngBuffer = 1 };
 
 // The observations of a data model (wn_model_api.h, kUsesData; null / 0 otherwise), read-only device memory shared by
-// every chain: what TrajChip::bind_data / load_row / obs_y / obs_group read.
+// every chain: what TrajChip::bind_data / load_row / obs_y / obs_group / obs_offset / obs_weight read.
 struct Observations {
   // x is num_obs rows of stride (= Dp) doubles, each laid out like a theta row and zero beyond num_params
   const double* x;
@@ -39,6 +39,11 @@ struct Observations {
   // rows are narrower than theta: stride = 128 * ceil(P / 128) doubles for P = num_params - num_groups - 1 columns
   const int32_t* group;  // [num_obs] (null for other models)
   int32_t num_groups;
+  // per-row offsets (eta_n += offset_n) and weights (the row's likelihood term times weight_n), sliced like y; null:
+  // absent.  WEIGHT SETS (chains_per_dataset > 0 with offsets == nullptr): x, y, offset and group are the one shared
+  // block of num_obs rows, weight is [sets][num_obs] and chain c reads set c / chains_per_dataset (stride num_obs)
+  const double* offset;  // [num_obs]
+  const double* weight;  // [num_obs], or [sets][num_obs]
 };
 
 // Every [C][Dp] plane is chain-major: one chain's vector is contiguous, rows are
@@ -115,7 +120,7 @@ struct Params {
 };
 // The layout the device models were compiled against (ModelAbi::sizeof_params, wn_model_api.h: kModelAbiVersion): a
 // change that moves these is a new ABI version.
-static_assert(sizeof(Observations) == 56 && sizeof(Params) == 448 && offsetof(Params, obs) == 392,
+static_assert(sizeof(Observations) == 72 && sizeof(Params) == 464 && offsetof(Params, obs) == 392,
               "wn::Params changed its layout: bump kModelAbiVersion");
 
 enum : uint32_t {

@@ -968,7 +968,7 @@ struct uses_data : std::false_type {};
 template <class M>
 struct uses_data<M, std::enable_if_t<M::kUsesData>> : std::true_type {};
 // ... and a data model that also reads a group index per observation (kUsesGroups: cx.num_groups() / obs_group(), rows
-// of P = num_params - num_groups - 1 columns at the narrower stride Params::data_stride)
+// of P = num_params - num_groups - 1 columns at the narrower stride Observations::stride)
 template <class M, class = void>
 struct uses_groups : std::false_type {};
 template <class M>
@@ -979,6 +979,12 @@ template <class M, class = void>
 struct scale_param : std::false_type {};
 template <class M>
 struct scale_param<M, std::enable_if_t<M::kScaleParam>> : std::true_type {};
+// ... and a data model that reads per-row offsets and weights (kUsesRowTerms: cx.has_offset() / obs_offset() /
+// has_weight() / obs_weight()); a model without the member compiles none of it
+template <class M, class = void>
+struct uses_row_terms : std::false_type {};
+template <class M>
+struct uses_row_terms<M, std::enable_if_t<M::kUsesRowTerms>> : std::true_type {};
 template <class M, bool Elementwise = M::kElementwise>
 struct StreamTraits {
   static constexpr bool kTwoPass = false, kHasSums = false, kHalo = false;

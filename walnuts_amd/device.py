@@ -139,6 +139,9 @@ def walnuts_device(
     print_callback=None,
     data=None,
     datasets=None,
+    offset=None,
+    weights=None,
+    weight_sets=None,
 ):
     """The device-model sibling of the reference's ``walnuts_pyfunc`` (pyfunc.py:45-286): same keywords, same result
     (a list of per-chain draw arrays carrying ``.warmup``).
@@ -176,7 +179,19 @@ def walnuts_device(
     [g*k, (g+1)*k) are conditioned on dataset g, and the results list is per chain as usual.  Warmup and sampling stop
     when EVERY dataset meets the rules (spread per dataset, R-hat per dataset).  With ``keep_on_device=True`` the call
     returns ``(results, [MarkovChains of dataset 0, of dataset 1, ...])``: views into one device block that stays alive
-    while any of them does.  Not with ``data``, ``devices`` or ``reference_streams``."""
+    while any of them does.  Not with ``data``, ``devices`` or ``reference_streams``.
+
+    ``offset=`` and ``weights=``: per-row offsets (eta_n = x_n . beta + offset_n: the exposure log E of a count model)
+    and weights >= 0 (logp = prior + sum_n weights_n ll_n; binomial counts as ``weights=m``, ``y=k/m``), arrays of shape
+    (num_obs,) with ``data=``, sequences with one array or None per dataset with ``datasets=``.  A run that carries
+    weights evaluates EVERY dataset in the weighted order of operations: a dataset whose entry is None gets weights of
+    1 and gives the bits of the call with ``weights=np.ones(num_obs)``, which differ in the last place from those of a
+    call without weights.
+
+    ``weight_sets=`` (with ``data=`` only): a (W, num_obs) array, W weight vectors over one shared block of rows --
+    K-fold refits, the bootstrap.  ``num_chains`` must be a multiple k of W, chains [g*k, (g+1)*k) use set g, and
+    everything said about ``datasets=`` holds with the sets as the datasets (stopping rules per set, one
+    ``MarkovChains`` view per set with ``keep_on_device=True``)."""
     lib = _ffi.load_library(lib_path)
     if data is not None and datasets is not None:
         raise ValueError("data and datasets are mutually exclusive")
@@ -211,8 +226,11 @@ def walnuts_device(
         raise ValueError("At least one of num_params or inits must be specified")
     if seed is None:
         seed = int(np.random.randint(0, 2**32 - 1, dtype=np.uint32))
-    obs = observations(lib, model, num_params, data, datasets)
+    obs = observations(lib, model, num_params, data, datasets, offset, weights, weight_sets)
     num_datasets = obs.num_datasets if datasets is not None else 1
+    if weight_sets is not None:
+        num_datasets = obs.num_weight_sets
+    several = datasets is not None or (weight_sets is not None and num_datasets > 1)
     mp = None if model_params is None else np.ascontiguousarray(np.asarray(model_params, dtype=np.float64))
     if mp is not None and mp.size != num_params:
         raise ValueError("model_params must have num_params entries")
@@ -301,7 +319,7 @@ def walnuts_device(
         if all_gather and devices is not None:
             return results, [MarkovChains(C.c_void_p(h), lib) for h in handles]
         chains = MarkovChains(chains_handle, lib)
-        if datasets is not None:   # one view per dataset's block of chains
+        if several:   # one view per dataset's (weight set's) block of chains
             lengths = final_lengths[num_chains:].astype(np.int64)
             return results, chains.chain_blocks(num_datasets, max_sampling_iter, lengths)
         return results, chains

@@ -59,7 +59,8 @@ def stream_version(lib_path: Optional[str] = None) -> int:
 
 class DeviceEngine:
     def __init__(self, model: int, dim: int, num_chains: int, cfg: Optional[_ffi.Config] = None,
-                 params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None, datasets=None):
+                 params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None, datasets=None,
+                 offset=None, weights=None, weight_sets=None):
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
         (num_obs, dim) and y of shape (num_obs,); copied to the device once.  `data=(x, y, group)` for a grouped model
         (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
@@ -73,7 +74,21 @@ class DeviceEngine:
         are conditioned on dataset g and evolve exactly as chains 0..k-1 of an engine built with data=(xg, yg) and
         seeded with chain_offset = g*k.  Per-dataset statistics: rhat_per_dataset(), warmup_spread_per_dataset();
         init_masses_from_grad(average=True) averages over each dataset's chains.  A grouped model takes triples
-        [(x0, y0, g0), ...] with the same number of columns in every x."""
+        [(x0, y0, g0), ...] with the same number of columns in every x.
+
+        `offset=` and `weights=` (every built-in data model): per-row terms of shape (num_obs,), eta_n = x_n . beta +
+        offset_n and logp = prior + sum_n weights_n * ll_n -- the exposure log E of a count model; frequency or
+        importance weights >= 0; binomial counts as weights=m, y=k/m (with weights the logistic models take y in
+        [0, 1]).  A row of weight 0 contributes exactly nothing.  With `datasets=` each is a sequence with one array (or
+        None) per dataset.  An engine that carries weights evaluates EVERY dataset in the weighted order of operations:
+        a dataset whose entry is None gets weights of 1 and gives the bits of a standalone engine built with
+        weights=np.ones(num_obs), which differ in the last place from those of an engine built without weights.
+
+        `weight_sets=` (with `data=` only): a (W, num_obs) array, W weight vectors over the one shared block of rows
+        -- K-fold refits, the bootstrap.  num_chains must be a multiple k of W; chains [g*k, (g+1)*k) use set g and
+        evolve exactly as chains 0..k-1 of an engine built with weights=weight_sets[g] and seeded with chain_offset =
+        g*k.  The sets are the engine's datasets: num_datasets == W and the per-dataset statistics are per set.  W == 1
+        is one weight vector, the same engine as weights=weight_sets[0] (num_datasets == 1)."""
         self.lib = _ffi.load_library(lib_path)
         self.cfg = cfg if cfg is not None else default_config(lib_path)
         self.C, self.D = int(num_chains), int(dim)
@@ -82,8 +97,9 @@ class DeviceEngine:
             raise ValueError("model params must have num_params entries")
         h, err = C.c_void_p(), C.c_void_p()
         pp = None if p is None else p.ctypes.data_as(_dp)
-        self._several = datasets is not None
-        obs = observations(self.lib, model, self.D, data, datasets)
+        obs = observations(self.lib, model, self.D, data, datasets, offset, weights, weight_sets)
+        # (one weight set is one weight vector: such an engine holds no datasets)
+        self._several = datasets is not None or (obs is not None and obs.num_weight_sets > 1)
         if obs is None:
             rc = self.lib.wn_engine_create(C.byref(h), model, dim, pp, num_chains, C.byref(self.cfg), C.byref(err))
         else:
