@@ -389,6 +389,27 @@ WALNUTS_HIP_EXPORT void wn_engine_destroy(wn_engine* e);
  * once.  No chain state is read or changed. */
 WALNUTS_HIP_EXPORT int wn_engine_eval(wn_engine* e, const double* theta, double* logp_out, double* grad_out,
                                       WalnutpyError** err);
+/* The POINTWISE log-likelihood of a data model, the sibling of wn_engine_eval: out[t][n] = l_n(theta_t), the full log
+ * density of row n of dataset `dataset` under position t -- constants included (-1/2 log 2 pi, -lgamma(y + 1)), the prior
+ * not, in the engine's arithmetic mode.  theta [T*D] in, out [T * rows of that dataset] out (host pointers); T is
+ * independent of the engine's num_chains.  Evaluated on the engine's own observation block: offsets and groups apply,
+ * weights are IGNORED (with per-trial l a weighted row would be w_n l_n); with weight sets the rows are the one shared
+ * block and `dataset` must be 0.  `config` errors: an engine without data; a model without the pointwise hook
+ * (wn_model_api.h kPointwise; the message names the model); a dataset out of range. */
+WALNUTS_HIP_EXPORT int wn_engine_log_lik(wn_engine* e, const double* theta, size_t num_theta, int dataset, double* out,
+                                         WalnutpyError** err);
+/* The log pointwise predictive density from draws that stay on the device: for every row n, over the draws theta of the
+ * chains that belong to the row's block (chain after chain, iteration after iteration, lengths respected),
+ *   lpd[n] = log mean exp l_n(theta),  mean[n], var[n] = mean and sample variance of l_n(theta),  count[n] = draws
+ * (csrc/wn_pointwise.h states the fold).  `chains` holds G*k chains, G = wn_engine_num_datasets(e): block g (chains
+ * [g*k, (g+1)*k)) is evaluated on dataset g's rows, or -- weight sets -- on the shared rows for set g.  Outputs (host
+ * pointers): [total rows] with datasets, [W][N] with weight sets, [N] for one block.  row_mask: uint8 shaped like the
+ * outputs (nonzero = evaluate), or NULL for every row; a row that is masked out is not evaluated and returns lpd = mean =
+ * var = NaN, count = 0.  A term of -inf contributes 0; lpd is -inf when every term is; NaN propagates; var is NaN with
+ * fewer than 2 draws.  The result is a function of the inputs alone (not of launch or workspace sizes).  `config`
+ * errors: as wn_engine_log_lik; chains->dims != num_params; num_chains not a multiple of G; chains on another device. */
+WALNUTS_HIP_EXPORT int wn_engine_log_predictive(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, double* lpd,
+                                                double* mean, double* var, int64_t* count, WalnutpyError** err);
 
 /* InitConfig (config.hpp:74-185): positions [C*D], masses [C*D] (masses, not inverse
  * masses), step sizes [C]; host pointers. */

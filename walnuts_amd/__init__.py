@@ -15,3 +15,4 @@ from .engine import (MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_LINEAR_REGRESSION, M
 from .device import WalnutsOutputArray, WarmupInfo, walnuts_device  # noqa: F401
 from . import models, summary  # noqa: F401,E402
 from .summary import MarkovChains, Summarizer  # noqa: F401,E402
+from .pointwise import PointwisePredictive, kfold_elpd, log_predictive  # noqa: F401,E402

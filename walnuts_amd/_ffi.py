@@ -121,6 +121,8 @@ SYMBOLS = [
     ("wn_engine_num_datasets", _i32, [_vp]),
     ("wn_engine_destroy", None, [_vp]),
     ("wn_engine_eval", _i32, [_vp, _dp, _dp, _dp, _errpp]),
+    ("wn_engine_log_lik", _i32, [_vp, _dp, _sz, _i32, _dp, _errpp]),
+    ("wn_engine_log_predictive", _i32, [_vp, _vp, C.POINTER(C.c_uint8), _dp, _dp, _dp, _i64p, _errpp]),
     ("wn_engine_set_positions", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_set_masses", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_set_step_sizes", _i32, [_vp, _dp, _errpp]),

@@ -38,6 +38,13 @@
 // Without weights the link receives the running sum as before and without offsets no add is issued: such an engine
 // computes what it computed before these fields existed, bit for bit.
 //
+// The POINTWISE hook (wn_model_api.h, kPointwise; wn_pointwise.h): pointwise() returns, in lane k, the likelihood term of
+// row n0 + k of a tile of 64 rows -- eta formed in the order above (pointwise_eta: the rows are streamed pair by pair,
+// nothing is kept for a gradient pass, eta of 64 rows is packed into the 64 lanes), then ONE evaluation of
+// Link::term(eta, y, r, 0.0, tab) on the full wavefront, the weighted path's expression.  Weights are never applied.
+// pointwise_const(y) is the constant the term drops, added by the kernel as its last operation:
+//   identity: -1/2 log 2 pi;   logit: 0 (Bernoulli per trial, the same expression for a proportion);   log: -lgamma(y + 1)
+//
 // Arithmetic: the prior variances arrive as reciprocals (host_params, as the diagonal normal's); the logistic mean is
 // one true division per block-row evaluation, 1 / (1 + exp(-|eta|)), and softplus(eta) = max(eta, 0) +
 // log(1 + exp(-|eta|)) never overflows.  exp / log are wnd::dexp / wnd::dlog with per-lane arguments (gather tables).
@@ -51,6 +58,9 @@
 
 namespace wn {
 
+// -1/2 log(2 pi), the normal density's constant (host side: rounded once where it is uploaded)
+constexpr long double kHalfLog2Pi = -0.918938533204672741780329736405617639L;
+
 struct IdentityLink {
   // r = y - eta; ll += -1/2 r^2
   template <class Cx, class Tab>
@@ -59,6 +69,7 @@ struct IdentityLink {
     return Cx::mad(-0.5 * r, r, ll);
   }
   static void check_y(double, bool) {}
+  static long double pointwise_const(double) { return kHalfLog2Pi; }
 };
 
 struct LogitLink {
@@ -82,6 +93,7 @@ struct LogitLink {
       throw std::invalid_argument("logistic_regression needs every y in {0, 1}");
     }
   }
+  static long double pointwise_const(double) { return 0.0L; }
 };
 
 struct LogLink {
@@ -94,6 +106,7 @@ struct LogLink {
     return Cx::mad(y, eta, ll) - mu;
   }
   static void check_y(double y, bool) { check_count(y, "Poisson regression"); }
+  static long double pointwise_const(double y) { return -lgammal(static_cast<long double>(y) + 1.0L); }
   // a count: finite, >= 0 and integer-valued
   static void check_count(double y, const char* model) {
     if (!(std::isfinite(y) && y >= 0.0 && y == std::floor(y)))
@@ -119,6 +132,46 @@ __device__ __forceinline__ double coord_value(const double (&v)[EPL], int c) {
 #pragma unroll
   for (int j = 0; j < EPL; ++j) mine = j == slot ? v[j] : mine;
   return lane_value(mine, (c >> 1) & 63);
+}
+
+// The pointwise hook's row pass (header comment): eta of rows n0 .. n0 + 63 of the block, row n0 + k in lane k, for the
+// rows whose lane holds `live` (the others: 0, and a pair of rows that is off issues no load).  nx: the slot pairs that
+// hold columns of x.  Rows pair up as in eval() -- (even, odd), the even row's sum in lanes 0-31 -- so the bits are its.
+template <int EPL, class Cx>
+__device__ __forceinline__ double pointwise_eta(Cx& cx, const double (&th)[EPL], int n0, bool live, int nx) {
+  static_assert(Cx::L == 64, "data models run one wavefront per chain");
+  const int liv = live ? 1 : 0;
+  double eta = 0.0;
+#pragma unroll 2
+  for (int k = 0; k < 64; k += 2) {
+    const bool la = lane_value(liv, k) != 0, lb = lane_value(liv, k + 1) != 0;
+    if (!(la || lb)) continue;
+    double xa[EPL], xb[EPL];
+    if (la) {
+      cx.load_row(n0 + k, xa);
+    } else {
+#pragma unroll
+      for (int j = 0; j < EPL; ++j) xa[j] = 0.0;
+    }
+    if (lb) {
+      cx.load_row(n0 + k + 1, xb);
+    } else {
+#pragma unroll
+      for (int j = 0; j < EPL; ++j) xb[j] = 0.0;
+    }
+    double da = 0.0, db = 0.0;
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      if ((j >> 1) < nx) {
+        da = Cx::mad(xa[j], th[j], da);
+        db = Cx::mad(xb[j], th[j], db);
+      }
+    }
+    const double packed = wave_sum_packed(da, db);
+    set_lane(eta, uni(packed), k);
+    set_lane(eta, lane_value(packed, 32), k + 1);
+  }
+  return eta;
 }
 
 template <class Link>
@@ -195,6 +248,19 @@ struct GlmModel {
     acc = acc + ll;
   }
   __device__ __forceinline__ static double finish(double sum, const Aux&, int) { return sum; }
+
+  // the pointwise hook (header comment): lane k's likelihood term of row n0 + k, constant dropped
+  static constexpr bool kPointwise = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static double pointwise(Cx& cx, const double (&th)[EPL], int n0, bool live) {
+    double eta = pointwise_eta<EPL>(cx, th, n0, live, EPL / 2);
+    const int n = n0 + opaque_lane_id();
+    const double y = live ? cx.obs_y(n) : 0.0;
+    if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n) : 0.0);
+    double r;
+    return Link::template term<Cx>(eta, y, r, 0.0, cx.gather_tab());
+  }
+  static long double pointwise_const(double y) { return Link::pointwise_const(y); }
 
   // host side: the prior variances -> their reciprocals (rounded once), and the observations' checks
   static void host_params(double* s2, int num_params) {

@@ -24,6 +24,10 @@
 // Per-row offsets and weights as in glm.h (its header states the order).  With weights the family's term is evaluated
 // with zero running sums (t, r, ds_n the row's own), then ds = ds + w * ds_n (a rounded product, then the add),
 // ll = Cx::mad(w, t, ll) and r = w * r; a row with w == 0 is discarded by select.
+//
+// The pointwise hook (glm.h's header; wn_pointwise.h): glm.h's pointwise_eta, then the family's term with zero running
+// sums on the full wavefront; what depends on s alone is computed once per draw and tile as above.  The constants the
+// terms drop: -lgamma(y + 1) (negative binomial), -1/2 log 2 pi (linear_regression_sigma).
 #pragma once
 
 #include "glm.h"
@@ -58,6 +62,7 @@ struct NegBinomialFamily {
     ds = ds + Cx::mad(k.phi, sp - dg, r);
   }
   static void check_y(double y, bool) { LogLink::check_count(y, "negative binomial regression"); }
+  static long double pointwise_const(double y) { return LogLink::pointwise_const(y); }
 };
 
 struct NormalSigmaFamily {
@@ -78,6 +83,7 @@ struct NormalSigmaFamily {
     ds = Cx::mad(d, r, ds) - 1.0;
   }
   static void check_y(double, bool) {}
+  static long double pointwise_const(double) { return kHalfLog2Pi; }
 };
 
 template <class Family>
@@ -176,6 +182,23 @@ struct GlmScaleModel {
     }
   }
   __device__ __forceinline__ static double finish(double sum, const Aux&, int) { return sum; }
+
+  // the pointwise hook (header comment): lane k's likelihood term of row n0 + k, constant dropped
+  static constexpr bool kPointwise = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static double pointwise(Cx& cx, const double (&th)[EPL], int n0, bool live) {
+    const double s = coord_value(th, cx.dim() - 1);
+    const double scale = wnd::dexp(s, cx.uniform_tab());
+    const typename Family::Consts k = Family::consts(s, scale, cx.uniform_tab());
+    double eta = pointwise_eta<EPL>(cx, th, n0, live, EPL / 2);
+    const int n = n0 + opaque_lane_id();
+    const double y = live ? cx.obs_y(n) : 0.0;
+    if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n) : 0.0);
+    double r, ll = 0.0, ds = 0.0;
+    Family::template term<Cx>(eta, y, k, cx.gather_tab(), r, ll, ds);
+    return ll;
+  }
+  static long double pointwise_const(double y) { return Family::pointwise_const(y); }
 
   // host side: the beta prior variances -> reciprocals, sigma_0 -> 1 / sigma_0^2 (each rounded once); the
   // observations' checks are the family's (x has num_params - 1 columns)

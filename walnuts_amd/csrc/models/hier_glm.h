@@ -29,6 +29,9 @@
 // tau = wnd::dexp(s) of the wave-uniform s, once per evaluation; the epilogue applies the formulas above with one
 // cx.sum1 (sum_j z_j S_j, or sum_j a_j^2).  A non-finite tau (s beyond +-709) takes no path of its own: the energy
 // turns non-finite and the trajectory treats it as every non-finite energy.
+//
+// The pointwise hook (glm.h's header; wn_pointwise.h): glm.h's pointwise_eta over the P columns, the group effect of the
+// tile's rows set into their lanes row by row as in step 1 above, the offset, then the link once on the full wavefront.
 #pragma once
 
 #include "glm.h"
@@ -176,6 +179,31 @@ struct HierGlmModel {
     }
   }
   __device__ __forceinline__ static double finish(double sum, const Aux&, int) { return sum; }
+
+  // the pointwise hook (header comment): lane k's likelihood term of row n0 + k, constant dropped
+  static constexpr bool kPointwise = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static double pointwise(Cx& cx, const double (&th)[EPL], int n0, bool live) {
+    const int D = cx.dim();
+    const int P = D - cx.num_groups() - 1;
+    const double tau = Centered ? 1.0 : wnd::dexp(coord(th, D - 1), cx.uniform_tab());
+    double eta = pointwise_eta<EPL>(cx, th, n0, live, (P + 127) >> 7);
+    const int n = n0 + opaque_lane_id();
+    const int grp = live ? cx.obs_group(n) : 0;
+    const int liv = live ? 1 : 0;
+    double v = 0.0;
+    for (int k = 0; k < 64; ++k) {
+      if (lane_value(liv, k) == 0) continue;
+      const double vk = coord(th, P + lane_value(grp, k));
+      set_lane(v, Centered ? vk : tau * vk, k);
+    }
+    eta = eta + v;
+    const double y = live ? cx.obs_y(n) : 0.0;
+    if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n) : 0.0);
+    double r;
+    return Link::template term<Cx>(eta, y, r, 0.0, cx.gather_tab());
+  }
+  static long double pointwise_const(double y) { return Link::pointwise_const(y); }
 
   // host side: the beta prior variances and the reserved entries -> reciprocals, sigma_tau -> 1 / sigma_tau^2 (each
   // rounded once); the observations' checks are the link's

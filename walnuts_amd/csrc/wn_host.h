@@ -16,6 +16,19 @@ struct WalnutpyError {
   WalnutpyErrorType type;
 };
 
+// Where a wn_chains keeps its draws (wn_summary.hip), for the translation units that read them in kernels of their own
+// (wn_engine_log_predictive): chain c's draw i is `dims` doubles at draws + off[c] + i * dims, i < len[c].
+struct wn_chains_layout {
+  const double* draws;
+  const long long* off;  // device [num_chains]
+  const int* len;        // device [num_chains]
+  const int* host_len;   // host [num_chains]
+  size_t num_chains, dims;
+  int device;
+  hipStream_t stream;    // work queued on the handle's own stream
+};
+void wn_chains_layout_of(const wn_chains* chains, wn_chains_layout* out);
+
 namespace {
 
 void hip_check(hipError_t e, const char* what) {

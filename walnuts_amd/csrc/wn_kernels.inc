@@ -8,6 +8,7 @@
 #include "wn_chip.h"
 #include "wn_init.h"
 #include "wn_launch.h"
+#include "wn_pointwise.h"
 #include "wn_traj.h"
 
 #define WN_CAT2(a, b) a##b
@@ -26,6 +27,9 @@ static_assert(!uses_row_terms<WN_MODEL_TYPE>::value || kUsesData, "kUsesRowTerms
 static_assert(!(scale_param<WN_MODEL_TYPE>::value && uses_groups<WN_MODEL_TYPE>::value),
               "kScaleParam and kUsesGroups do not combine (wn_model_api.h)");
 static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }
+// the pointwise log-likelihood kernels (wn_pointwise.h) exist for data models that declare the hook
+static constexpr bool kPointwise = is_pointwise<WN_MODEL_TYPE>::value;
+static_assert(!kPointwise || kUsesData, "kPointwise needs kUsesData (wn_model_api.h)");
 
 void WN_CAT(launch_transition_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem, hipStream_t stream,
                                                const Params& p) {
@@ -132,6 +136,56 @@ void WN_CAT(launch_eval_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem
 #undef WN_X
   throw std::invalid_argument("no kernel for this geometry");
 }
+
+// wn_engine_log_lik / wn_engine_log_predictive: one wavefront per work item, the engine's elements per lane and
+// arithmetic mode (pointwise_kernel / pointwise_combine_kernel, wn_pointwise.h).  Instantiated for a model that declares
+// the hook only.
+namespace {
+template <class M, bool kOn = is_pointwise<M>::value>
+struct PointwiseLaunch {
+  static void launch(const Geometry&, int, hipStream_t, bool, const PointwiseParams&) {}
+  static void combine(int, hipStream_t, const PointwiseCombineParams&) {}
+  static void consts(const double*, size_t, double*) {}
+};
+template <class M>
+struct PointwiseLaunch<M, true> {
+  static void launch(const Geometry& g, int grid, hipStream_t stream, bool fma, const PointwiseParams& q) {
+#define WN_X(NW, EPL)                                                                            \
+  if constexpr (NW == 1) {                                                                       \
+    if (!g.mem && g.nw == 1 && g.epl == EPL) {                                                   \
+      if (fma)                                                                                   \
+        hipLaunchKernelGGL((pointwise_kernel<M, EPL, true>), dim3(grid), dim3(64), 0, stream, q);  \
+      else                                                                                       \
+        hipLaunchKernelGGL((pointwise_kernel<M, EPL, false>), dim3(grid), dim3(64), 0, stream, q); \
+      return;                                                                                    \
+    }                                                                                            \
+  }
+    WN_FOR_EACH_GEOMETRY(WN_X)
+#undef WN_X
+    throw std::invalid_argument("no pointwise kernel for this geometry");
+  }
+  static void combine(int grid, hipStream_t stream, const PointwiseCombineParams& q) {
+    hipLaunchKernelGGL((pointwise_combine_kernel<kPointwiseCombineBlock>), dim3(grid), dim3(kPointwiseCombineBlock), 0,
+                       stream, q);
+  }
+  static void consts(const double* y, size_t n, double* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = static_cast<double>(M::pointwise_const(y[i]));
+  }
+};
+}  // namespace
+void WN_CAT(launch_pointwise_, WN_MODEL_TAG)(const Geometry& g, int grid, hipStream_t stream, bool fma,
+                                              const PointwiseParams& q) {
+  PointwiseLaunch<WN_MODEL_TYPE>::launch(g, grid, stream, fma, q);
+}
+void WN_CAT(launch_pointwise_combine_, WN_MODEL_TAG)(int grid, hipStream_t stream, const PointwiseCombineParams& q) {
+  PointwiseLaunch<WN_MODEL_TYPE>::combine(grid, stream, q);
+}
+void WN_CAT(pointwise_consts_, WN_MODEL_TAG)(const double* y, size_t n, double* out) {
+  PointwiseLaunch<WN_MODEL_TYPE>::consts(y, n, out);
+}
+static const PointwiseOps WN_CAT(kPointwiseOps_, WN_MODEL_TAG) = {&WN_CAT(launch_pointwise_, WN_MODEL_TAG),
+                                                                  &WN_CAT(launch_pointwise_combine_, WN_MODEL_TAG),
+                                                                  &WN_CAT(pointwise_consts_, WN_MODEL_TAG)};
 
 void WN_CAT(prepare_, WN_MODEL_TAG)(const Geometry& g, size_t smem) {
   if (g.mem) {
@@ -258,7 +312,8 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     &WN_CAT(host_data_, WN_MODEL_TAG),
     uses_groups<WN_MODEL_TYPE>::value,
     scale_param<WN_MODEL_TYPE>::value,
-    uses_row_terms<WN_MODEL_TYPE>::value};
+    uses_row_terms<WN_MODEL_TYPE>::value,
+    kPointwise ? &WN_CAT(kPointwiseOps_, WN_MODEL_TAG) : nullptr};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

@@ -12,6 +12,8 @@
 namespace wn {
 
 struct InitParams;
+struct PointwiseParams;
+struct PointwiseCombineParams;
 
 // NW wavefronts cooperate on one chain, each lane holds EPL elements of every vector:
 // padded dimension Dp = 64*NW*EPL.  `mem`: the streaming backend (TrajMem) -- vectors in HBM, any dimension; epl is 0 then.
@@ -167,6 +169,15 @@ inline int padded_dim(const Geometry& g, int dim) {
 // One entry per device model, filled in by the model's own translation unit (WN_REGISTER_MODEL in
 // wn_model_api.h) when the library is loaded.  Nothing else in the host code names a model: adding one is
 // writing its header and a three-line .hip file ("Adding a device model").
+// The pointwise log-likelihood of a data model that declares the hook (wn_model_api.h, kPointwise; wn_pointwise.h)
+struct PointwiseOps {
+  // log_lik / the per-chain fold of the predictive pass (pointwise_kernel), one wavefront per work item
+  void (*launch)(const Geometry&, int grid, hipStream_t, bool fma, const PointwiseParams&);
+  // the across-chain merge of the predictive pass (pointwise_combine_kernel)
+  void (*launch_combine)(int grid, hipStream_t, const PointwiseCombineParams&);
+  // host side: out[n] = c_n(y[n]), the constant the row term drops (long double, rounded once)
+  void (*row_consts)(const double* y, size_t num_obs, double* out);
+};
 struct ModelOps {
   int id;
   const char* name;
@@ -191,6 +202,7 @@ struct ModelOps {
   bool uses_groups;  // a data model that reads a group index per observation (kUsesGroups)
   bool scale_param;  // a flat data model whose last coordinate is a scale parameter, not a column of x (kScaleParam)
   bool uses_row_terms;  // a data model that reads per-row offsets and weights (kUsesRowTerms)
+  const PointwiseOps* pointwise;  // the pointwise log-likelihood (kPointwise); null: the model declares no such hook
 };
 constexpr int kMaxModels = 64;
 inline const ModelOps** model_table() {
@@ -205,7 +217,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 13;
+constexpr int kModelAbiVersion = 14;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

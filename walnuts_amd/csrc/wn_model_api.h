@@ -77,6 +77,21 @@
 //     // has_weight() / obs_weight() below.  wn_engine_create refuses offsets or weights for a model without this member,
 //     // and a model without it compiles nothing of them.
 //     static constexpr bool kUsesRowTerms = true;
+//     // ... and, on top of kUsesData, the POINTWISE log-likelihood (wn_pointwise.h: wn_engine_log_lik,
+//     // wn_engine_log_predictive -- held-out log predictive density, WAIC, K-fold scores from draws that stay on the
+//     // device).  pointwise() returns, in lane k, the likelihood term of row n0 + k of a tile of 64 consecutive rows
+//     // (n0 a multiple of 64, wave-uniform) for the lanes whose `live` is set -- the other lanes' rows are absent or
+//     // masked out: read nothing of theirs, return anything.  The prior is NOT part of it and weights are NEVER
+//     // applied (cx.has_weight() is false here).  The built-in models form eta in the order models/glm.h states, pack
+//     // the eta of the 64 rows into the 64 lanes (pointwise_eta) and evaluate their link ONCE, with a zero running sum
+//     // -- the expression of eval()'s weighted path, so the bits are eval()'s.  pointwise_const(y) is, on the HOST in
+//     // long double, whatever constant of the row's full log density the term leaves out (0 if none); it is rounded
+//     // once, kept in a device array beside y, and added by the kernel as its last operation.  An engine whose model
+//     // lacks this member refuses the two entry points with a `config` error that names the model.
+//     static constexpr bool kPointwise = true;
+//     template <int EPL, class Cx>
+//     static double pointwise(Cx& cx, const double (&theta)[EPL], int n0, bool live);
+//     static long double pointwise_const(double y);
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -108,6 +123,8 @@
 //                                             evaluation or per block, never per element
 //   cx.obs_offset(n), cx.obs_weight(n)        offset_n / weight_n (0 <= n < num_obs; only where has_*() is true) -- with
 //                                             weight sets, of the set the chain is conditioned on; the model cannot tell
+// (pointwise() receives the same calls over the block of rows being scored -- wn_pointwise.h, PointwiseCx -- with
+// cx.has_weight() false; cx.sum1 / element0 / shift are not offered there)
 // The wavefront primitives of the platform layer (wave_sum_packed, lane_value, set_lane, uni, ...: wn_gfx950.h, with
 // the same association order under the CPU emulation) are available to eval(); models/glm.h uses them to reduce two
 // rows' dot products per butterfly.

@@ -767,6 +767,11 @@ int wn_chains_upload(wn_chains** out, const double* draws_host, size_t dims, con
 }
 
 void wn_chains_destroy(wn_chains* ch) { delete ch; }
+}  // extern "C"
+void wn_chains_layout_of(const wn_chains* ch, wn_chains_layout* out) {
+  *out = wn_chains_layout{ch->x, ch->off.p, ch->len.p, ch->h_len.data(), ch->C, ch->D, ch->device, ch->stream};
+}
+extern "C" {
 size_t wn_chains_num_chains(const wn_chains* ch) { return ch->C; }
 size_t wn_chains_dims(const wn_chains* ch) { return ch->D; }
 size_t wn_chains_num_draws(const wn_chains* ch) { return static_cast<size_t>(ch->N); }

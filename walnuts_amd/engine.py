@@ -100,6 +100,10 @@ class DeviceEngine:
         obs = observations(self.lib, model, self.D, data, datasets, offset, weights, weight_sets)
         # (one weight set is one weight vector: such an engine holds no datasets)
         self._several = datasets is not None or (obs is not None and obs.num_weight_sets > 1)
+        # rows per dataset (the pointwise entry points size their outputs with them)
+        self._row_sizes = None if obs is None else (
+            [int(obs.num_obs)] if datasets is None else [int(n) for n in np.diff(obs.arrays[3])])
+        self._weight_sets = obs is not None and obs.num_weight_sets > 1
         if obs is None:
             rc = self.lib.wn_engine_create(C.byref(h), model, dim, pp, num_chains, C.byref(self.cfg), C.byref(err))
         else:
@@ -204,6 +208,47 @@ class DeviceEngine:
         g = np.empty((self.C, self.D))
         self._call(self.lib.wn_engine_eval, th.ctypes.data_as(_dp), lp.ctypes.data_as(_dp), g.ctypes.data_as(_dp))
         return lp, g
+
+    def _rows(self, dataset=None):
+        """Rows of dataset `dataset`; None: of every output row (all datasets, or W * N with weight sets)."""
+        sizes = self._row_sizes
+        if sizes is None:   # an engine without data: the library refuses the call (a `config` error naming the model)
+            return 1 if dataset is not None else (1,)
+        if dataset is None:
+            return (self.num_datasets * sizes[0],) if self._weight_sets else (int(sum(sizes)),)
+        if not 0 <= dataset < (1 if self._weight_sets else len(sizes)):
+            raise ValueError("weight sets share one block of rows: dataset must be 0" if self._weight_sets
+                             else "dataset must be in [0, num_datasets)")
+        return sizes[dataset]
+
+    def log_lik(self, theta, dataset: int = 0):
+        """The POINTWISE log-likelihood [T, N] of dataset `dataset` at positions theta [T, D] (wn_engine_log_lik): entry
+        [t, n] is the full log density of row n under theta[t] -- constants included, the prior not, offsets and groups
+        applied, weights IGNORED -- in the engine's arithmetic mode.  T is independent of the engine's num_chains; with
+        weight sets the rows are the one shared block (dataset 0).  No chain state is read or changed."""
+        th = _f64(theta).reshape(-1, self.D)
+        out = np.empty((th.shape[0], self._rows(int(dataset))))
+        self._call(self.lib.wn_engine_log_lik, th.ctypes.data_as(_dp), th.shape[0], int(dataset), out.ctypes.data_as(_dp))
+        return out
+
+    def log_predictive(self, chains, row_mask=None):
+        """(lpd, mean, var, count) per row from draws that stay on the device (wn_engine_log_predictive): `chains` is a
+        MarkovChains of G * k chains, G = num_datasets; block g is scored on dataset g's rows (weight sets: on the shared
+        rows, as set g).  lpd = log mean exp l_n over the block's draws, mean / var the moments of l_n, count the draws.
+        Arrays of shape [total rows], or [W, N] with weight sets; `row_mask` of that shape (nonzero = evaluate) or None:
+        a masked row is not evaluated and gives NaN, NaN, NaN, 0.  walnuts_amd.log_predictive wraps this."""
+        shape = self._rows() if not self._weight_sets else (self.num_datasets, self._row_sizes[0])
+        mask = None
+        if row_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(row_mask) != 0, dtype=np.uint8)
+            if mask.shape != tuple(shape):
+                raise ValueError(f"row_mask must have shape {tuple(shape)}, got {mask.shape}")
+        lpd, mean, var = (np.empty(shape) for _ in range(3))
+        count = np.empty(shape, dtype=np.int64)
+        self._call(self.lib.wn_engine_log_predictive, chains._h,
+                   None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), lpd.ctypes.data_as(_dp),
+                   mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp), count.ctypes.data_as(_ffi._i64p))
+        return lpd, mean, var, count
 
     # ---- state
     def _get(self, fn, shape, dtype=np.float64, ptr=_dp):
