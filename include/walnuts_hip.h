@@ -585,6 +585,27 @@ WALNUTS_HIP_EXPORT int wn_internal_sqrt_probe(const double* x, double* y, size_t
  * fn 0 dlog1p(x), 1 dsoftplus(x), 2 dlgamma_diff(x, phi) = lgamma(x + phi) - lgamma(phi), 3 ddigamma_diff(x, phi) =
  * psi(x + phi) - psi(phi) (phi is read for fn 2 and 3 only, but must hold n doubles).  -> 0, or -1 */
 WALNUTS_HIP_EXPORT int wn_internal_count_math_probe(const double* x, const double* phi, double* y, size_t n, int fn);
+/* (internal, for the tests) the rest of csrc/wn_devmath.h evaluated on the device for n host arguments.
+ * fn: 0 dexp(x), 1 dlog(x), 2 dlog_normal(x), 3 dexp_weight(x), 4 dpow_pos(x, y), 5 dsincospi(x) (out0 = sin, out1 = cos),
+ * 6 x / SharedDivisor(y).  y is read for fn 4 and 6, out1 written for fn 5; both may be null otherwise.
+ * tab, the provider of the exp / log table entries (fn 5 and 6 read none and run the same way under each):
+ *   0 ArrayTables: one argument per lane, out[n];
+ *   1 UniformTab: one argument per wavefront iteration, made wave-uniform; every lane stores its result: out[64 n],
+ *     out[64 i + lane] (the 64 must agree);
+ *   2 GatherTab: one argument per lane, all 64 lanes take part (the last wavefront with clamped indices), out[n];
+ *     dpow_pos then takes the y of the first argument of each run of 64 for the whole run.
+ * -> 0, -1 (device error) or -2 (bad argument) */
+WALNUTS_HIP_EXPORT int wn_internal_math_probe(const double* x, const double* y, double* out0, double* out1, size_t n,
+                                              int fn, int tab);
+/* ... the counter-based streams for indices first .. first + n - 1 of (seed, chain, transition, stream): normals == 0:
+ * out0 = stream_uniform(index); otherwise (out0, out1) = stream_normal_pair(pair = index) under table provider `tab`
+ * (sizes as above) */
+WALNUTS_HIP_EXPORT int wn_internal_stream_probe(unsigned long long seed, unsigned int chain, unsigned int transition,
+                                                unsigned int stream, unsigned int first, size_t n, int normals, int tab,
+                                                double* out0, double* out1);
+/* ... raw Philox4x32 with rounds = 7 or 10: counters ctr[4 n], keys key[2 n] -> out[4 n] */
+WALNUTS_HIP_EXPORT int wn_internal_philox_probe(const unsigned int* ctr, const unsigned int* key, unsigned int* out,
+                                                size_t n, int rounds);
 WALNUTS_HIP_EXPORT void wn_internal_reference_normals(unsigned int seed, unsigned int stream, size_t num_chains,
                                                       size_t count_per_chain, int fresh_per_chain, double scale,
                                                       double* out);

@@ -382,7 +382,7 @@ struct Adam {
 // ---------------------------------------------------------------------------
 // Device arithmetic (WNO_MATH_PORTABLE) divides a plane's elements by the estimator's weight the way the kernels do
 // (walnuts_amd/csrc/wn_devmath.h, SharedDivisor): r = 1 / w once, then q0 = a r, q = fma(fma(-q0, w, a), r, q0) -- the
-// correctly rounded quotient for every finite numerator in the normal range (the all-ones significand aside), restated
+// correctly rounded quotient for every finite numerator of magnitude 2^-960 or more (the all-ones significand aside), restated
 // here operation for operation so that the comparison is exact in the corner cases too.  Reference arithmetic: `/`.
 static inline double div_shared(double a, double w, double r) {
   const double q0 = a * r;

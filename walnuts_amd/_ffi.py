@@ -100,6 +100,9 @@ SYMBOLS = [
      _MODEL_ARGS + _SAMPLING_ARGS + _DEVICES_ARGS + _RESIDENT_ARGS + [_errpp]),
     ("wn_internal_sqrt_probe", _i32, [_dp, _dp, _sz, _i32]),
     ("wn_internal_count_math_probe", _i32, [_dp, _dp, _dp, _sz, _i32]),
+    ("wn_internal_math_probe", _i32, [_dp, _dp, _dp, _dp, _sz, _i32, _i32]),
+    ("wn_internal_stream_probe", _i32, [_u64, _u32, _u32, _u32, _u32, _sz, _i32, _i32, _dp, _dp]),
+    ("wn_internal_philox_probe", _i32, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _sz, _i32]),
     ("wn_model_data_columns", _i32, [_i32, _i32, _i32]),
     ("wn_internal_reference_normals", None, [C.c_uint, C.c_uint, _sz, _sz, _i32, _dbl, _dp]),
     ("walnutpie_ess", _i32, [_dp, _i32, _i32, C.POINTER(C.c_int), _i32, _dp, _errpp]),

@@ -58,10 +58,20 @@ WND_HD double fmad(double a, double b, double c) { return __builtin_fma(a, b, c)
 // from ONE true division, q0 = RN(a r), the exact remainder a - b q0 in one fused multiply-add and q = RN(q0 + rem r)
 // is the correctly rounded quotient (Markstein, "Computation of elementary functions on the IBM RISC System/6000",
 // 1990; Cornea, Harrison, Tang 2002, thm. 1) -- three instructions where v_div_scale / v_rcp / v_div_fmas / v_div_fixup
-// take eleven.  It equals IEEE division for every finite numerator with a quotient in the normal range, unless b's
-// significand is all ones (RN(1/b) then sits on a rounding boundary; a weight `discount * w + 1` never has been);
-// a non-finite numerator gives NaN where division gives +-inf.  The oracle's device-order mode restates exactly these
-// three operations, so parity with it is bit for bit in every case; tests/test_portable_math.py compares with `/`.
+// take eleven.  It equals IEEE division for every finite numerator of magnitude 2^-960 or more with a quotient in the
+// normal range, unless b's significand is all ones (RN(1/b) then sits on a rounding boundary; a weight
+// `discount * w + 1` never has been).  Below that the remainder, a multiple of ulp(b) ulp(q0) ~ 2^-105 |a|, stops being
+// representable and the quotient may be off by one unit in the last place: certain to be absent from 2^-968 up, seen
+// only in the lowest binades (test_shared_divisor_domain of tests/test_devmath_sim.py counts them per exponent and
+// asserts none from 2^-960 up).  The estimator's numerators are a draw or a gradient minus its running mean, and sums of
+// such differences squared.  An argument, not a reading of every test's planes: a non-zero difference of two doubles is
+// no smaller than an ulp of the smaller one, so a difference below 2^-960 needs a coordinate, a gradient or a mean
+// below 2^-907 = 1e-273 in magnitude, a squared one a difference below 2^-480 and so an operand below 2^-427 = 1e-129;
+// a draw from a continuous density does not land there, and parity with the oracle does not depend on it (below).
+// A zero numerator of either sign gives +0 (`/` keeps the sign); a non-finite numerator gives NaN where division gives
+// +-inf.  The oracle's device-order mode restates
+// exactly these three operations, so parity with it is bit for bit in every case; tests/test_portable_math.py and
+// tests/test_devmath_sim.py compare with `/`, tests/test_devmath_gpu.py the device with the host.
 struct SharedDivisor {
   double b, r;
   WND_HD explicit SharedDivisor(double d) : b(d), r(1.0 / d) {}
