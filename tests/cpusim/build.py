@@ -7,8 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "walnuts_amd", "csrc")
 OUT = os.path.join(HERE, "libwalnuts_sim.so")
-SOURCES = ["wn_engine.hip", "wn_sample.hip", "wn_summary.hip"] + sorted(
-    f for f in os.listdir(CSRC) if f.startswith("wn_kernels_") and f.endswith(".hip"))  # one per device model
+# every translation unit of the library (among them one wn_kernels_<model>.hip per device model), as the Makefile takes them
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.startswith("wn_") and f.endswith(".hip"))
 
 
 def build(force: bool = False) -> str:
@@ -31,7 +31,7 @@ def build(force: bool = False) -> str:
         objs.append(o)
         procs.append(subprocess.Popen(
             ["g++", "-x", "c++", "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-pthread", "-DWN_CPU_SIM",
-             "-DWN_SIM_GEOMETRIES", "-I", HERE, "-I", CSRC, "-c", s, "-o", own(o)]))
+             "-DWN_SIM_GEOMETRIES", "-DWN_ENGINE_UNITS", "-I", HERE, "-I", CSRC, "-c", s, "-o", own(o)]))
     for p in procs:
         if p.wait() != 0:
             raise RuntimeError("cpusim compile failed")
@@ -50,7 +50,7 @@ def build_with_models(model_sources, out_dir: str) -> str:
         o = os.path.join(out_dir, os.path.basename(src) + ".sim.o")
         subprocess.check_call(
             ["g++", "-x", "c++", "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-pthread", "-DWN_CPU_SIM",
-             "-DWN_SIM_GEOMETRIES", "-I", HERE, "-I", CSRC, "-I", os.path.dirname(src), "-c", src, "-o", o])
+             "-DWN_SIM_GEOMETRIES", "-DWN_ENGINE_UNITS", "-I", HERE, "-I", CSRC, "-I", os.path.dirname(src), "-c", src, "-o", o])
         objs.append(o)
     tag = "_".join(os.path.splitext(os.path.basename(m))[0].replace("wn_kernels_", "") for m in model_sources)
     out = os.path.join(out_dir, f"libwalnuts_sim_{tag}.so")   # (a name of its own: loaded libraries are cached by path)

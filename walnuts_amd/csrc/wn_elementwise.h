@@ -1,4 +1,5 @@
-// wn_elementwise.h -- element-wise kernels around the transition kernel (included by wn_engine.hip only).
+// wn_elementwise.h -- element-wise kernels around the transition kernel (its kernels are static: included by
+// wn_engine_elementwise.hip only).
 #pragma once
 
 #include "wn_devmath.h"

@@ -1,0 +1,170 @@
+// wn_engine_pointwise.hip -- pointwise scoring on the engine's observation block (wn_pointwise.h): wn_engine_log_lik,
+// the log-likelihood of every row at given parameter vectors, and wn_engine_log_predictive, the log predictive density
+// of every row over the draws of a wn_chains.
+#include "wn_engine.h"
+
+#include "wn_pointwise.h"
+
+namespace {
+// the engine's model as the pointwise entry points need it: a data model with the hook, or a `config` error
+const wn::PointwiseOps& pointwise_ops(const wn_engine* e) {
+  const wn::ModelOps& ops = wn::model_ops(e->model);
+  if (!ops.uses_data || e->obs.x == nullptr)
+    throw std::invalid_argument(std::string(ops.name) + " model: this engine holds no data, there is no pointwise "
+                                "log-likelihood to evaluate (create it with wn_engine_create_observed)");
+  if (ops.pointwise == nullptr || e->data_const.p == nullptr)
+    throw std::invalid_argument(std::string(ops.name) + " model declares no pointwise log-likelihood (wn_model_api.h: "
+                                "kPointwise, pointwise(), pointwise_const())");
+  return *ops.pointwise;
+}
+// block g of the engine's rows: where its data rows start, how many there are, and where its outputs start
+struct RowBlock {
+  int64_t row0, out0;
+  int32_t rows;
+};
+RowBlock row_block(const wn_engine* e, const std::vector<int64_t>& offsets, int g) {
+  if (!offsets.empty()) return RowBlock{offsets[g], offsets[g], static_cast<int32_t>(offsets[g + 1] - offsets[g])};
+  return RowBlock{0, static_cast<int64_t>(g) * e->obs.num_obs, e->obs.num_obs};  // one block, or weight set g of it
+}
+std::vector<int64_t> host_offsets(wn_engine* e) {
+  std::vector<int64_t> off;
+  if (e->obs.offsets != nullptr) {
+    off.resize(static_cast<size_t>(e->num_datasets) + 1);
+    HIP_OK(hipMemcpyAsync(off.data(), e->data_offsets.p, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+  }
+  return off;
+}
+// work items -> workgroups: one each up to a cap (the kernel strides beyond it; any grid gives the same bits)
+int pointwise_grid(int64_t items) {
+  int64_t cap = int64_t{1} << 20;
+  if (const char* v = std::getenv("WALNUTS_AMD_POINTWISE_GRID")) cap = std::max<int64_t>(1, std::atoll(v));
+  return static_cast<int>(std::max<int64_t>(1, std::min(items, cap)));
+}
+// what both passes hand the kernel about block b; num_items = `units` (parameter vectors, or chains) x the block's tiles
+wn::PointwiseParams pointwise_params(const wn_engine* e, const RowBlock& b, bool predictive, size_t units) {
+  wn::PointwiseParams Q{};
+  Q.obs = e->obs;
+  Q.row_const = e->data_const.p;
+  Q.dim = e->D;
+  Q.predictive = predictive ? 1 : 0;
+  Q.row0 = b.row0;
+  Q.num_rows = b.rows;
+  Q.num_tiles = (b.rows + wn::kPointwiseTile - 1) / wn::kPointwiseTile;
+  Q.num_items = static_cast<int64_t>(units) * Q.num_tiles;
+  return Q;
+}
+}  // namespace
+
+extern "C" {
+
+int wn_engine_log_lik(wn_engine* e, const double* theta, size_t num_theta, int dataset, double* out, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (e == nullptr || theta == nullptr || out == nullptr) throw std::invalid_argument("null argument");
+    const wn::PointwiseOps& pw = pointwise_ops(e);
+    if (num_theta < 1 || num_theta > 0x7fffffffull) throw std::invalid_argument("num_theta must be in [1, 2^31)");
+    const bool sets = e->obs.chains_per_dataset > 0 && e->obs.offsets == nullptr;
+    if (dataset < 0 || dataset >= (sets ? 1 : e->num_datasets))
+      throw std::invalid_argument(sets ? "weight sets share one block of rows: dataset must be 0"
+                                       : "dataset must be in [0, wn_engine_num_datasets)");
+    e->use_device();
+    const RowBlock b = row_block(e, host_offsets(e), dataset);
+    const size_t T = num_theta, D = static_cast<size_t>(e->D), N = static_cast<size_t>(b.rows);
+    DevBuf<double> th, ll;
+    th.alloc(T * D);
+    ll.alloc(T * N);
+    HIP_OK(hipMemcpyAsync(th.p, theta, T * D * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    wn::PointwiseParams Q = pointwise_params(e, b, /*predictive=*/false, T);
+    Q.theta = th.p;
+    Q.out = ll.p;
+    pw.launch(e->geo, pointwise_grid(Q.num_items), e->stream, e->cfg.fused_multiply_add != 0, Q);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, ll.p, T * N * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int wn_engine_log_predictive(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, double* lpd, double* mean,
+                             double* var, int64_t* count, WalnutpyError** err) {
+  return guarded(err, [&] {
+    if (e == nullptr || chains == nullptr || lpd == nullptr || mean == nullptr || var == nullptr || count == nullptr)
+      throw std::invalid_argument("null argument");
+    const wn::PointwiseOps& pw = pointwise_ops(e);
+    wn_chains_layout ch{};
+    wn_chains_layout_of(chains, &ch);
+    if (ch.dims != static_cast<size_t>(e->D))
+      throw std::invalid_argument("the chains hold draws of " + std::to_string(ch.dims) + " dimensions, the engine's model has " +
+                                  std::to_string(e->D) + " parameters");
+    const size_t G = static_cast<size_t>(e->num_datasets);
+    if (ch.num_chains % G != 0)
+      throw std::invalid_argument("the number of chains (" + std::to_string(ch.num_chains) + ") must be a multiple of the "
+                                  "engine's datasets / weight sets (" + std::to_string(G) + "): block g of the chains is "
+                                  "scored on dataset g");
+    if (ch.device != e->device) throw std::invalid_argument("the chains live on another device than the engine");
+    const size_t k = ch.num_chains / G;
+    e->use_device();
+    HIP_OK(hipStreamSynchronize(ch.stream));  // (uploads queued on the handle's own stream)
+    const std::vector<int64_t> offsets = host_offsets(e);
+    const bool sets = e->obs.chains_per_dataset > 0 && e->obs.offsets == nullptr;
+    const size_t total = sets ? G * static_cast<size_t>(e->obs.num_obs) : e->data_rows;
+    DevBuf<double> d_lpd, d_mean, d_var, partial, state;
+    DevBuf<long long> d_count;
+    DevBuf<uint8_t> d_mask;
+    d_lpd.alloc(total);
+    d_mean.alloc(total);
+    d_var.alloc(total);
+    d_count.alloc(total);
+    if (row_mask != nullptr) {
+      d_mask.alloc(total);
+      HIP_OK(hipMemcpyAsync(d_mask.p, row_mask, total, hipMemcpyHostToDevice, e->stream));
+    }
+    // the per-chain partials of one SLAB of chains at a time: the merge carries its state from slab to slab in chain
+    // order, so the workspace's size changes nothing
+    size_t budget = size_t{256} << 20;
+    if (const char* v = std::getenv("WALNUTS_AMD_POINTWISE_WORKSPACE")) budget = static_cast<size_t>(std::max(1ll, std::atoll(v)));
+    for (size_t g = 0; g < G; ++g) {
+      const RowBlock b = row_block(e, offsets, static_cast<int>(g));
+      const size_t N = static_cast<size_t>(b.rows);
+      const size_t slab = std::max<size_t>(1, std::min(k, budget / (4 * sizeof(double) * N)));
+      if (partial.n < 4 * slab * N) partial.alloc(4 * slab * N);
+      if (slab < k && state.n < 5 * N) state.alloc(5 * N);
+      for (size_t c0 = 0; c0 < k; c0 += slab) {
+        const size_t nc = std::min(slab, k - c0);
+        wn::PointwiseParams Q = pointwise_params(e, b, /*predictive=*/true, nc);
+        Q.draws = ch.draws;
+        Q.chain_off = ch.off;
+        Q.chain_len = ch.len;
+        Q.chain0 = static_cast<int32_t>(g * k + c0);
+        Q.slab_chains = static_cast<int32_t>(nc);
+        Q.mask = row_mask != nullptr ? d_mask.p + b.out0 : nullptr;
+        Q.partial = partial.p;
+        pw.launch(e->geo, pointwise_grid(Q.num_items), e->stream, e->cfg.fused_multiply_add != 0, Q);
+        HIP_OK(hipGetLastError());
+        wn::PointwiseCombineParams R{};
+        R.partial = partial.p;
+        R.chain_len = ch.len;
+        R.chain0 = Q.chain0;
+        R.slab_chains = Q.slab_chains;
+        R.num_rows = b.rows;
+        R.first = c0 == 0 ? 1 : 0;
+        R.last = c0 + nc == k ? 1 : 0;
+        R.mask = Q.mask;
+        R.state = state.p;
+        R.lpd = d_lpd.p + b.out0;
+        R.mean = d_mean.p + b.out0;
+        R.var = d_var.p + b.out0;
+        R.count = d_count.p + b.out0;
+        pw.launch_combine(static_cast<int>((N + wn::kPointwiseCombineBlock - 1) / wn::kPointwiseCombineBlock), e->stream, R);
+        HIP_OK(hipGetLastError());
+      }
+    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "count goes out as int64");
+    HIP_OK(hipMemcpyAsync(lpd, d_lpd.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(mean, d_mean.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(var, d_var.p, total * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(count, d_count.p, total * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+  });
+}
+
+}  // extern "C"

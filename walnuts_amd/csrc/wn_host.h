@@ -29,9 +29,9 @@ struct wn_chains_layout {
 };
 void wn_chains_layout_of(const wn_chains* chains, wn_chains_layout* out);
 
-namespace {
-
-void hip_check(hipError_t e, const char* what) {
+// (inline and plain templates, not an anonymous namespace: struct wn_engine (wn_engine.h) holds DevBufs and is one type
+// across the engine's translation units, and a unit that uses only some of these stays quiet under -Wall)
+inline void hip_check(hipError_t e, const char* what) {
   if (e != hipSuccess) {
     std::stringstream ss;
     ss << "HIP error in " << what << ": " << hipGetErrorString(e);
@@ -71,7 +71,5 @@ struct DevBuf {
   }
   ~DevBuf() { release(); }
 };
-
-}  // namespace
 
 #endif  // WN_HOST_H

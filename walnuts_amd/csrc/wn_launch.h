@@ -225,7 +225,7 @@ struct ModelAbi {
 }  // namespace wn
 // A device model compiled at RUN time (walnuts_amd/models.py: one hipcc -shared of its five-line translation unit
 // against these headers) is a shared object of its own; when it is loaded, its registration lands in the LIBRARY's
-// registry through this exported entry point (wn_engine.hip) -- the device counterpart of handing the reference a
+// registry through this exported entry point (wn_engine_build.hip) -- the device counterpart of handing the reference a
 // LOGP_CFUNC / numba cfunc (python/src/walnutpie/walnutpy.cpp:131-132, pyfunc.py:216).  -> 0, or -1 (wn_model_error()).
 extern "C" __attribute__((visibility("default"))) int wn_plugin_register_model(const void* ops, const void* abi);
 namespace wn {

@@ -1,4 +1,4 @@
-// wn_monitor.h -- the host side's share of the cross-chain monitors, common to the engine (wn_engine.hip) and the
+// wn_monitor.h -- the host side's share of the cross-chain monitors, common to the engine (wn_engine_elementwise.hip) and the
 // sampling driver's controllers (wn_sample.hip).
 #pragma once
 
