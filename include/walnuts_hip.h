@@ -410,6 +410,35 @@ WALNUTS_HIP_EXPORT int wn_engine_log_lik(wn_engine* e, const double* theta, size
  * errors: as wn_engine_log_lik; chains->dims != num_params; num_chains not a multiple of G; chains on another device. */
 WALNUTS_HIP_EXPORT int wn_engine_log_predictive(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, double* lpd,
                                                 double* mean, double* var, int64_t* count, WalnutpyError** err);
+/* PREDICTIONS of a data model, the sibling of wn_engine_log_lik: for position t and row n of dataset `dataset`,
+ *   eta_out[t][n] = the linear predictor (x_n . beta, the group effect, the offset: as the likelihood forms it),
+ *   mean_out[t][n] = E[y | theta_t, x_n],   var_out[t][n] = Var[y | theta_t, x_n]
+ * in the engine's arithmetic mode (csrc/wn_predict.h holds the table per family).  theta [T*D] in, each output [T * rows
+ * of that dataset] (host pointers); any output may be NULL, not all.  x, groups and offsets are read; y and weights
+ * never are: a logistic row with binomial weights is predicted per trial.  Non-finite values follow IEEE (an
+ * overflowing Poisson link gives inf).  `config` errors: an engine without data; a model without the predict hook
+ * (wn_model_api.h kPredict; the message names the model); a dataset out of range; every output NULL. */
+WALNUTS_HIP_EXPORT int wn_engine_predict(wn_engine* e, const double* theta, size_t num_theta, int dataset, double* eta_out,
+                                         double* mean_out, double* var_out, WalnutpyError** err);
+/* The moments of the predictions over draws that stay on the device, with the shapes, block semantics, mask and slabbed
+ * workspace of wn_engine_log_predictive: for every row n, over the draws of the chains of the row's block,
+ *   eta_mean[n], eta_var[n] = mean and sample variance of eta;  mean[n], mean_var[n] = those of E[y | theta, x_n];
+ *   noise_var[n] = the mean of Var[y | theta, x_n];  count[n] = draws
+ * (csrc/wn_predict.h states the fold).  The predictive variance of a new observation is noise_var + mean_var (the law of
+ * total variance).  A row that is masked out is not evaluated and returns NaN everywhere and count = 0; the variances
+ * are NaN with fewer than 2 draws.  The result is a function of the inputs alone.  `config` errors: as
+ * wn_engine_predict; chains->dims != num_params; num_chains not a multiple of G; chains on another device. */
+WALNUTS_HIP_EXPORT int wn_engine_predict_fold(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, double* eta_mean,
+                                              double* eta_var, double* mean, double* mean_var, double* noise_var,
+                                              int64_t* count, WalnutpyError** err);
+/* One predicted quantity per draw, as chains of their own: *out owns a new device block [k][max_len][rows] -- chain c,
+ * draw i, row n holds eta (what == 0) or E[y | theta, x_n] (what == 1) of draw i of chain block * k + c, the same bits
+ * wn_engine_predict gives for that draw -- with the source chains' lengths, on the engine's device; every wn_summary_*
+ * function applies (quantiles, R-hat, ESS, MCSE of a prediction); release it with wn_chains_destroy.  `block` selects
+ * the k chains and the rows of dataset / weight set `block`.  `config` errors: as wn_engine_predict_fold; block out of
+ * range; what outside {0, 1}.  A failed allocation is a `generic` error that states the bytes asked for. */
+WALNUTS_HIP_EXPORT int wn_engine_predict_chains(wn_engine* e, wn_chains* chains, int block, int what, wn_chains** out,
+                                                WalnutpyError** err);
 
 /* InitConfig (config.hpp:74-185): positions [C*D], masses [C*D] (masses, not inverse
  * masses), step sizes [C]; host pointers. */

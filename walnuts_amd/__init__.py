@@ -16,3 +16,4 @@ from .device import WalnutsOutputArray, WarmupInfo, walnuts_device  # noqa: F401
 from . import models, summary  # noqa: F401,E402
 from .summary import MarkovChains, Summarizer  # noqa: F401,E402
 from .pointwise import PointwisePredictive, kfold_elpd, log_predictive  # noqa: F401,E402
+from .predict import Prediction, predict, predict_draws  # noqa: F401,E402

@@ -45,6 +45,10 @@
 // pointwise_const(y) is the constant the term drops, added by the kernel as its last operation:
 //   identity: -1/2 log 2 pi;   logit: 0 (Bernoulli per trial, the same expression for a proportion);   log: -lgamma(y + 1)
 //
+// The PREDICT hook (wn_model_api.h, kPredict; wn_predict.h): predict() leaves in lane k the triple (eta, mu, v) of row
+// n0 + k -- eta formed as pointwise() forms it (pointwise_eta, the offset), then ONE evaluation of Link::response on the
+// full wavefront: mu = E y and v = Var y given eta (wn_predict.h holds the table).  y and the weights are never read.
+//
 // Arithmetic: the prior variances arrive as reciprocals (host_params, as the diagonal normal's); the logistic mean is
 // one true division per block-row evaluation, 1 / (1 + exp(-|eta|)), and softplus(eta) = max(eta, 0) +
 // log(1 + exp(-|eta|)) never overflows.  exp / log are wnd::dexp / wnd::dlog with per-lane arguments (gather tables).
@@ -68,6 +72,12 @@ struct IdentityLink {
     r = y - eta;
     return Cx::mad(-0.5 * r, r, ll);
   }
+  // mean and variance of y given eta: unit noise
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static void response(double eta, double& mu, double& v, const Tab&) {
+    mu = eta;
+    v = 1.0;
+  }
   static void check_y(double, bool) {}
   static long double pointwise_const(double) { return kHalfLog2Pi; }
 };
@@ -83,6 +93,14 @@ struct LogitLink {
     const double sp = (eta > 0.0 ? eta : 0.0) + wnd::dlog(1.0 + e, tab);
     r = y - mu;
     return Cx::mad(y, eta, ll) - sp;
+  }
+  // per trial: mu as term() computes it for its residual; v = mu (1 - mu) as (e * d) * d, without the cancellation
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static void response(double eta, double& mu, double& v, const Tab& tab) {
+    const double e = wnd::dexp(-__builtin_fabs(eta), tab);
+    const double d = 1.0 / (1.0 + e);
+    mu = eta >= 0.0 ? d : e * d;
+    v = (e * d) * d;
   }
   // (with weights y may be a proportion: k successes in m trials are weight m and y = k / m)
   static void check_y(double y, bool weighted) {
@@ -104,6 +122,12 @@ struct LogLink {
     const double mu = wnd::dexp(eta, tab);
     r = y - mu;
     return Cx::mad(y, eta, ll) - mu;
+  }
+  // Poisson: mean and variance are exp(eta) (inf where it overflows)
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static void response(double eta, double& mu, double& v, const Tab& tab) {
+    mu = wnd::dexp(eta, tab);
+    v = mu;
   }
   static void check_y(double y, bool) { check_count(y, "Poisson regression"); }
   static long double pointwise_const(double y) { return -lgammal(static_cast<long double>(y) + 1.0L); }
@@ -261,6 +285,16 @@ struct GlmModel {
     return Link::template term<Cx>(eta, y, r, 0.0, cx.gather_tab());
   }
   static long double pointwise_const(double y) { return Link::pointwise_const(y); }
+
+  // the predict hook (header comment): lane k's (eta, mu, v) of row n0 + k
+  static constexpr bool kPredict = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void predict(Cx& cx, const double (&th)[EPL], int n0, bool live, double& eta,
+                                                 double& mu, double& v) {
+    eta = pointwise_eta<EPL>(cx, th, n0, live, EPL / 2);
+    if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n0 + opaque_lane_id()) : 0.0);
+    Link::template response<Cx>(eta, mu, v, cx.gather_tab());
+  }
 
   // host side: the prior variances -> their reciprocals (rounded once), and the observations' checks
   static void host_params(double* s2, int num_params) {

@@ -28,6 +28,10 @@
 // The pointwise hook (glm.h's header; wn_pointwise.h): glm.h's pointwise_eta, then the family's term with zero running
 // sums on the full wavefront; what depends on s alone is computed once per draw and tile as above.  The constants the
 // terms drop: -lgamma(y + 1) (negative binomial), -1/2 log 2 pi (linear_regression_sigma).
+//
+// The predict hook (glm.h's header; wn_predict.h): glm.h's pointwise_eta and the offset, then the family's response on
+// the full wavefront with scale = exp(s) computed once per draw and tile: the negative binomial's mu = exp(eta),
+// v = mu + kappa mu^2 as Cx::mad(kappa * mu, mu, mu) with kappa = scale; the normal's mu = eta, v = scale * scale.
 #pragma once
 
 #include "glm.h"
@@ -61,6 +65,12 @@ struct NegBinomialFamily {
     ll = (ll + (Cx::mad(y, t, lg))) - yp * sp;
     ds = ds + Cx::mad(k.phi, sp - dg, r);
   }
+  // E y = exp(eta), Var y = mu + kappa mu^2 (NB2), kappa = scale
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static void response(double eta, double scale, double& mu, double& v, const Tab& tab) {
+    mu = wnd::dexp(eta, tab);
+    v = Cx::mad(scale * mu, mu, mu);
+  }
   static void check_y(double y, bool) { LogLink::check_count(y, "negative binomial regression"); }
   static long double pointwise_const(double y) { return LogLink::pointwise_const(y); }
 };
@@ -81,6 +91,12 @@ struct NormalSigmaFamily {
     r = d * k.isig2;
     ll = Cx::mad(-0.5 * d, r, ll) - k.s;
     ds = Cx::mad(d, r, ds) - 1.0;
+  }
+  // E y = eta, Var y = sigma^2, sigma = scale
+  template <class Cx, class Tab>
+  __device__ __forceinline__ static void response(double eta, double scale, double& mu, double& v, const Tab&) {
+    mu = eta;
+    v = scale * scale;
   }
   static void check_y(double, bool) {}
   static long double pointwise_const(double) { return kHalfLog2Pi; }
@@ -199,6 +215,17 @@ struct GlmScaleModel {
     return ll;
   }
   static long double pointwise_const(double y) { return Family::pointwise_const(y); }
+
+  // the predict hook (header comment): lane k's (eta, mu, v) of row n0 + k
+  static constexpr bool kPredict = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void predict(Cx& cx, const double (&th)[EPL], int n0, bool live, double& eta,
+                                                 double& mu, double& v) {
+    const double scale = wnd::dexp(coord_value(th, cx.dim() - 1), cx.uniform_tab());
+    eta = pointwise_eta<EPL>(cx, th, n0, live, EPL / 2);
+    if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n0 + opaque_lane_id()) : 0.0);
+    Family::template response<Cx>(eta, scale, mu, v, cx.gather_tab());
+  }
 
   // host side: the beta prior variances -> reciprocals, sigma_0 -> 1 / sigma_0^2 (each rounded once); the
   // observations' checks are the family's (x has num_params - 1 columns)

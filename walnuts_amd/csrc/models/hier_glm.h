@@ -32,6 +32,8 @@
 //
 // The pointwise hook (glm.h's header; wn_pointwise.h): glm.h's pointwise_eta over the P columns, the group effect of the
 // tile's rows set into their lanes row by row as in step 1 above, the offset, then the link once on the full wavefront.
+// The predict hook (glm.h's header; wn_predict.h) forms eta in the same way and evaluates Link::response in place of
+// Link::term; y is never read.
 #pragma once
 
 #include "glm.h"
@@ -204,6 +206,29 @@ struct HierGlmModel {
     return Link::template term<Cx>(eta, y, r, 0.0, cx.gather_tab());
   }
   static long double pointwise_const(double y) { return Link::pointwise_const(y); }
+
+  // the predict hook (header comment): lane k's (eta, mu, v) of row n0 + k
+  static constexpr bool kPredict = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void predict(Cx& cx, const double (&th)[EPL], int n0, bool live, double& eta,
+                                                 double& mu, double& v) {
+    const int D = cx.dim();
+    const int P = D - cx.num_groups() - 1;
+    const double tau = Centered ? 1.0 : wnd::dexp(coord(th, D - 1), cx.uniform_tab());
+    eta = pointwise_eta<EPL>(cx, th, n0, live, (P + 127) >> 7);
+    const int n = n0 + opaque_lane_id();
+    const int grp = live ? cx.obs_group(n) : 0;
+    const int liv = live ? 1 : 0;
+    double u = 0.0;
+    for (int k = 0; k < 64; ++k) {
+      if (lane_value(liv, k) == 0) continue;
+      const double uk = coord(th, P + lane_value(grp, k));
+      set_lane(u, Centered ? uk : tau * uk, k);
+    }
+    eta = eta + u;
+    if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n) : 0.0);
+    Link::template response<Cx>(eta, mu, v, cx.gather_tab());
+  }
 
   // host side: the beta prior variances and the reserved entries -> reciprocals, sigma_tau -> 1 / sigma_tau^2 (each
   // rounded once); the observations' checks are the link's

@@ -1,7 +1,7 @@
 // wn_engine.h -- the engine's state: struct wn_engine behind the C ABI in include/walnuts_hip.h, shared by the engine's
 // translation units (wn_engine.hip: transitions, initialisation and the plain entry points; wn_engine_build.hip:
 // wn_engine_create*; wn_engine_elementwise.hip: the element-wise passes and cross-chain monitors;
-// wn_engine_pointwise.hip: pointwise scoring).  Members that launch a kernel are only declared here: each is defined in
+// wn_engine_pointwise.hip: pointwise scoring; wn_engine_predict.hip: predictions).  Members that launch a kernel are only declared here: each is defined in
 // the one unit that includes the kernels' header, so no unit compiles another's kernels.
 #ifndef WN_ENGINE_H
 #define WN_ENGINE_H
@@ -224,5 +224,37 @@ struct wn_engine {
   void step(bool warm, double* draws_dev, int64_t draws_stride, int fused = 1, int64_t draws_tstride = 0,
             bool flush_only = false);
 };
+
+// ---- the row passes over the observation block (wn_engine_pointwise.hip, wn_engine_predict.hip) ----------------------
+// block g of the engine's rows: where its data rows start, how many there are, and where its outputs start
+struct RowBlock {
+  int64_t row0, out0;
+  int32_t rows;
+};
+inline RowBlock row_block(const wn_engine* e, const std::vector<int64_t>& offsets, int g) {
+  if (!offsets.empty()) return RowBlock{offsets[g], offsets[g], static_cast<int32_t>(offsets[g + 1] - offsets[g])};
+  return RowBlock{0, static_cast<int64_t>(g) * e->obs.num_obs, e->obs.num_obs};  // one block, or weight set g of it
+}
+inline std::vector<int64_t> host_offsets(wn_engine* e) {
+  std::vector<int64_t> off;
+  if (e->obs.offsets != nullptr) {
+    off.resize(static_cast<size_t>(e->num_datasets) + 1);
+    HIP_OK(hipMemcpyAsync(off.data(), e->data_offsets.p, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+  }
+  return off;
+}
+// work items -> workgroups: one each up to a cap (the kernel strides beyond it; any grid gives the same bits)
+inline int pointwise_grid(int64_t items) {
+  int64_t cap = int64_t{1} << 20;
+  if (const char* v = std::getenv("WALNUTS_AMD_POINTWISE_GRID")) cap = std::max<int64_t>(1, std::atoll(v));
+  return static_cast<int>(std::max<int64_t>(1, std::min(items, cap)));
+}
+// bytes of the per-chain partials a fold keeps at a time (one SLAB of chains; the merge carries its state across slabs)
+inline size_t pointwise_workspace_bytes() {
+  size_t budget = size_t{256} << 20;
+  if (const char* v = std::getenv("WALNUTS_AMD_POINTWISE_WORKSPACE")) budget = static_cast<size_t>(std::max(1ll, std::atoll(v)));
+  return budget;
+}
 
 #endif  // WN_ENGINE_H

@@ -1,7 +1,8 @@
 // wn_engine.hip -- host side of the C ABI in include/walnuts_hip.h: drives the persistent transition kernel and the
 // initialisation kernels over the engine's chain-major HBM planes (wn_engine.h), and holds the plain entry points:
 // setters, getters, timing, streams.  The other units around the same state: wn_engine_build.hip (wn_engine_create*),
-// wn_engine_elementwise.hip (adapter start / freeze, cross-chain monitors), wn_engine_pointwise.hip (pointwise scoring).
+// wn_engine_elementwise.hip (adapter start / freeze, cross-chain monitors), wn_engine_pointwise.hip (pointwise scoring),
+// wn_engine_predict.hip (predictions).
 #include "wn_engine.h"
 
 #include "wn_init.h"
@@ -611,5 +612,6 @@ int wn_engine_release_stream(wn_engine* e, void* stream, WalnutpyError** err) {
 #include "wn_engine_build.hip"
 #include "wn_engine_elementwise.hip"
 #include "wn_engine_pointwise.hip"
+#include "wn_engine_predict.hip"
 #include "wn_probes.hip"
 #endif

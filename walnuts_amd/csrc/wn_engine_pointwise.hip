@@ -17,30 +17,6 @@ const wn::PointwiseOps& pointwise_ops(const wn_engine* e) {
                                 "kPointwise, pointwise(), pointwise_const())");
   return *ops.pointwise;
 }
-// block g of the engine's rows: where its data rows start, how many there are, and where its outputs start
-struct RowBlock {
-  int64_t row0, out0;
-  int32_t rows;
-};
-RowBlock row_block(const wn_engine* e, const std::vector<int64_t>& offsets, int g) {
-  if (!offsets.empty()) return RowBlock{offsets[g], offsets[g], static_cast<int32_t>(offsets[g + 1] - offsets[g])};
-  return RowBlock{0, static_cast<int64_t>(g) * e->obs.num_obs, e->obs.num_obs};  // one block, or weight set g of it
-}
-std::vector<int64_t> host_offsets(wn_engine* e) {
-  std::vector<int64_t> off;
-  if (e->obs.offsets != nullptr) {
-    off.resize(static_cast<size_t>(e->num_datasets) + 1);
-    HIP_OK(hipMemcpyAsync(off.data(), e->data_offsets.p, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipStreamSynchronize(e->stream));
-  }
-  return off;
-}
-// work items -> workgroups: one each up to a cap (the kernel strides beyond it; any grid gives the same bits)
-int pointwise_grid(int64_t items) {
-  int64_t cap = int64_t{1} << 20;
-  if (const char* v = std::getenv("WALNUTS_AMD_POINTWISE_GRID")) cap = std::max<int64_t>(1, std::atoll(v));
-  return static_cast<int>(std::max<int64_t>(1, std::min(items, cap)));
-}
 // what both passes hand the kernel about block b; num_items = `units` (parameter vectors, or chains) x the block's tiles
 wn::PointwiseParams pointwise_params(const wn_engine* e, const RowBlock& b, bool predictive, size_t units) {
   wn::PointwiseParams Q{};
@@ -120,8 +96,7 @@ int wn_engine_log_predictive(wn_engine* e, wn_chains* chains, const uint8_t* row
     }
     // the per-chain partials of one SLAB of chains at a time: the merge carries its state from slab to slab in chain
     // order, so the workspace's size changes nothing
-    size_t budget = size_t{256} << 20;
-    if (const char* v = std::getenv("WALNUTS_AMD_POINTWISE_WORKSPACE")) budget = static_cast<size_t>(std::max(1ll, std::atoll(v)));
+    const size_t budget = pointwise_workspace_bytes();
     for (size_t g = 0; g < G; ++g) {
       const RowBlock b = row_block(e, offsets, static_cast<int>(g));
       const size_t N = static_cast<size_t>(b.rows);

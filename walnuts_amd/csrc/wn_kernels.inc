@@ -9,6 +9,7 @@
 #include "wn_init.h"
 #include "wn_launch.h"
 #include "wn_pointwise.h"
+#include "wn_predict.h"
 #include "wn_traj.h"
 
 #define WN_CAT2(a, b) a##b
@@ -30,6 +31,9 @@ static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }
 // the pointwise log-likelihood kernels (wn_pointwise.h) exist for data models that declare the hook
 static constexpr bool kPointwise = is_pointwise<WN_MODEL_TYPE>::value;
 static_assert(!kPointwise || kUsesData, "kPointwise needs kUsesData (wn_model_api.h)");
+// ... and the prediction kernels (wn_predict.h)
+static constexpr bool kPredict = is_predict<WN_MODEL_TYPE>::value;
+static_assert(!kPredict || kUsesData, "kPredict needs kUsesData (wn_model_api.h)");
 
 void WN_CAT(launch_transition_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem, hipStream_t stream,
                                                const Params& p) {
@@ -187,6 +191,48 @@ static const PointwiseOps WN_CAT(kPointwiseOps_, WN_MODEL_TAG) = {&WN_CAT(launch
                                                                   &WN_CAT(launch_pointwise_combine_, WN_MODEL_TAG),
                                                                   &WN_CAT(pointwise_consts_, WN_MODEL_TAG)};
 
+// wn_engine_predict / wn_engine_predict_fold / wn_engine_predict_chains: one wavefront per work item, the engine's
+// elements per lane and arithmetic mode (predict_kernel / predict_combine_kernel, wn_predict.h).  Instantiated for a
+// model that declares the hook only.
+namespace {
+template <class M, bool kOn = is_predict<M>::value>
+struct PredictLaunch {
+  static void launch(const Geometry&, int, hipStream_t, bool, const PredictParams&) {}
+  static void combine(int, hipStream_t, const PredictCombineParams&) {}
+};
+template <class M>
+struct PredictLaunch<M, true> {
+  static void launch(const Geometry& g, int grid, hipStream_t stream, bool fma, const PredictParams& q) {
+#define WN_X(NW, EPL)                                                                          \
+  if constexpr (NW == 1) {                                                                     \
+    if (!g.mem && g.nw == 1 && g.epl == EPL) {                                                 \
+      if (fma)                                                                                 \
+        hipLaunchKernelGGL((predict_kernel<M, EPL, true>), dim3(grid), dim3(64), 0, stream, q);  \
+      else                                                                                     \
+        hipLaunchKernelGGL((predict_kernel<M, EPL, false>), dim3(grid), dim3(64), 0, stream, q); \
+      return;                                                                                  \
+    }                                                                                          \
+  }
+    WN_FOR_EACH_GEOMETRY(WN_X)
+#undef WN_X
+    throw std::invalid_argument("no predict kernel for this geometry");
+  }
+  static void combine(int grid, hipStream_t stream, const PredictCombineParams& q) {
+    hipLaunchKernelGGL((predict_combine_kernel<kPointwiseCombineBlock>), dim3(grid), dim3(kPointwiseCombineBlock), 0,
+                       stream, q);
+  }
+};
+}  // namespace
+void WN_CAT(launch_predict_, WN_MODEL_TAG)(const Geometry& g, int grid, hipStream_t stream, bool fma,
+                                            const PredictParams& q) {
+  PredictLaunch<WN_MODEL_TYPE>::launch(g, grid, stream, fma, q);
+}
+void WN_CAT(launch_predict_combine_, WN_MODEL_TAG)(int grid, hipStream_t stream, const PredictCombineParams& q) {
+  PredictLaunch<WN_MODEL_TYPE>::combine(grid, stream, q);
+}
+static const PredictOps WN_CAT(kPredictOps_, WN_MODEL_TAG) = {&WN_CAT(launch_predict_, WN_MODEL_TAG),
+                                                              &WN_CAT(launch_predict_combine_, WN_MODEL_TAG)};
+
 void WN_CAT(prepare_, WN_MODEL_TAG)(const Geometry& g, size_t smem) {
   if (g.mem) {
     if constexpr (!kHasStreaming) {
@@ -313,7 +359,8 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     uses_groups<WN_MODEL_TYPE>::value,
     scale_param<WN_MODEL_TYPE>::value,
     uses_row_terms<WN_MODEL_TYPE>::value,
-    kPointwise ? &WN_CAT(kPointwiseOps_, WN_MODEL_TAG) : nullptr};
+    kPointwise ? &WN_CAT(kPointwiseOps_, WN_MODEL_TAG) : nullptr,
+    kPredict ? &WN_CAT(kPredictOps_, WN_MODEL_TAG) : nullptr};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

@@ -14,6 +14,8 @@ namespace wn {
 struct InitParams;
 struct PointwiseParams;
 struct PointwiseCombineParams;
+struct PredictParams;
+struct PredictCombineParams;
 
 // NW wavefronts cooperate on one chain, each lane holds EPL elements of every vector:
 // padded dimension Dp = 64*NW*EPL.  `mem`: the streaming backend (TrajMem) -- vectors in HBM, any dimension; epl is 0 then.
@@ -178,6 +180,13 @@ struct PointwiseOps {
   // host side: out[n] = c_n(y[n]), the constant the row term drops (long double, rounded once)
   void (*row_consts)(const double* y, size_t num_obs, double* out);
 };
+// The predictions of a data model that declares the hook (wn_model_api.h, kPredict; wn_predict.h)
+struct PredictOps {
+  // the matrix, the generated chains and the per-chain fold (predict_kernel), one wavefront per work item
+  void (*launch)(const Geometry&, int grid, hipStream_t, bool fma, const PredictParams&);
+  // the across-chain merge of the fold (predict_combine_kernel)
+  void (*launch_combine)(int grid, hipStream_t, const PredictCombineParams&);
+};
 struct ModelOps {
   int id;
   const char* name;
@@ -203,6 +212,7 @@ struct ModelOps {
   bool scale_param;  // a flat data model whose last coordinate is a scale parameter, not a column of x (kScaleParam)
   bool uses_row_terms;  // a data model that reads per-row offsets and weights (kUsesRowTerms)
   const PointwiseOps* pointwise;  // the pointwise log-likelihood (kPointwise); null: the model declares no such hook
+  const PredictOps* predict;      // eta, mean and variance of a row (kPredict); null: the model declares no such hook
 };
 constexpr int kMaxModels = 64;
 inline const ModelOps** model_table() {
@@ -217,7 +227,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 14;
+constexpr int kModelAbiVersion = 15;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

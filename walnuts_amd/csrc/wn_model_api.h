@@ -92,6 +92,17 @@
 //     template <int EPL, class Cx>
 //     static double pointwise(Cx& cx, const double (&theta)[EPL], int n0, bool live);
 //     static long double pointwise_const(double y);
+//     // ... and, on top of kUsesData, PREDICTIONS (wn_predict.h: wn_engine_predict, wn_engine_predict_fold,
+//     // wn_engine_predict_chains -- the linear predictor, the expected response and its variance of new rows from draws
+//     // that stay on the device).  predict() leaves, in lane k, the triple of row n0 + k of a tile of 64 consecutive rows
+//     // (n0 a multiple of 64, wave-uniform; `live` as for pointwise()): eta, the linear predictor; mu = E[y | theta,
+//     // x_n]; v = Var[y | theta, x_n].  It reads x, the group and the offset, NEVER y or the weights.  The built-in
+//     // models form eta exactly as their pointwise() does and evaluate Link::response / Family::response -- the sibling
+//     // of term() -- ONCE on the full wavefront (wn_predict.h holds the table of mu and v per family).  An engine whose
+//     // model lacks this member refuses the three entry points with a `config` error that names the model.
+//     static constexpr bool kPredict = true;
+//     template <int EPL, class Cx>
+//     static void predict(Cx& cx, const double (&theta)[EPL], int n0, bool live, double& eta, double& mu, double& v);
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -124,7 +135,7 @@
 //   cx.obs_offset(n), cx.obs_weight(n)        offset_n / weight_n (0 <= n < num_obs; only where has_*() is true) -- with
 //                                             weight sets, of the set the chain is conditioned on; the model cannot tell
 // (pointwise() receives the same calls over the block of rows being scored -- wn_pointwise.h, PointwiseCx -- with
-// cx.has_weight() false; cx.sum1 / element0 / shift are not offered there)
+// cx.has_weight() false; cx.sum1 / element0 / shift are not offered there; predict() receives the same cx)
 // The wavefront primitives of the platform layer (wave_sum_packed, lane_value, set_lane, uni, ...: wn_gfx950.h, with
 // the same association order under the CPU emulation) are available to eval(); models/glm.h uses them to reduce two
 // rows' dot products per butterfly.

@@ -82,12 +82,13 @@ struct PointwiseParams {
 };
 
 // What Model::pointwise sees as `cx`: the data-model calls of wn_model_api.h over ONE block of rows (row indices are
-// relative to the block), one wavefront.
-template <class Model, int EPL, bool FMA>
+// relative to the block), one wavefront.  P: the kernel's parameter struct -- obs, dim, row0, num_rows are read
+// (wn_predict.h hands its own).
+template <class Model, int EPL, bool FMA, class P = PointwiseParams>
 struct PointwiseCx {
   static constexpr int L = 64;
   static constexpr int NP = EPL / 2;
-  const PointwiseParams& Q;
+  const P& Q;
   int tid;
   LaneTables tabs;
   const double* obs_x;
@@ -96,7 +97,7 @@ struct PointwiseCx {
   const double* obs_ov;
   int x_stride;
 
-  __device__ __forceinline__ explicit PointwiseCx(const PointwiseParams& q) : Q(q) {
+  __device__ __forceinline__ explicit PointwiseCx(const P& q) : Q(q) {
     tid = opaque_lane_id();
     tabs.load(tid);
     x_stride = uses_groups<Model>::value ? Q.obs.stride : L * EPL;

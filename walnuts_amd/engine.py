@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _ffi
 from ._observations import _f64, observations
+from .summary import MarkovChains
 
 MODEL_STD_NORMAL, MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_RW1 = 0, 1, 2, 3
 # models conditioned on data (walnuts_amd/csrc/models/glm.h): params = the prior variances, data = (x, y)
@@ -249,6 +250,47 @@ class DeviceEngine:
                    None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), lpd.ctypes.data_as(_dp),
                    mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp), count.ctypes.data_as(_ffi._i64p))
         return lpd, mean, var, count
+
+    def predict(self, theta, dataset: int = 0):
+        """(eta, mean, var), each [T, N]: the linear predictor, E[y | theta, x_n] and Var[y | theta, x_n] of every row of
+        dataset `dataset` at positions theta [T, D] (wn_engine_predict), in the engine's arithmetic mode.  eta is formed
+        as the likelihood forms it (groups and offsets applied); y and weights are never read, so a logistic row with
+        binomial weights is predicted per trial.  No chain state is read or changed."""
+        th = _f64(theta).reshape(-1, self.D)
+        eta, mean, var = (np.empty((th.shape[0], self._rows(int(dataset)))) for _ in range(3))
+        self._call(self.lib.wn_engine_predict, th.ctypes.data_as(_dp), th.shape[0], int(dataset), eta.ctypes.data_as(_dp),
+                   mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp))
+        return eta, mean, var
+
+    def predict_fold(self, chains, row_mask=None):
+        """(eta_mean, eta_var, mean, mean_var, noise_var, count) per row from draws that stay on the device
+        (wn_engine_predict_fold): the moments of eta and of E[y | theta, x_n] over the draws of the row's block, the mean
+        of Var[y | theta, x_n], and the number of draws.  Blocks, shapes and `row_mask` as for log_predictive; a masked
+        row is not evaluated and gives NaN everywhere and count 0.  walnuts_amd.predict wraps this."""
+        shape = self._rows() if not self._weight_sets else (self.num_datasets, self._row_sizes[0])
+        mask = None
+        if row_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(row_mask) != 0, dtype=np.uint8)
+            if mask.shape != tuple(shape):
+                raise ValueError(f"row_mask must have shape {tuple(shape)}, got {mask.shape}")
+        out = tuple(np.empty(shape) for _ in range(5))
+        count = np.empty(shape, dtype=np.int64)
+        self._call(self.lib.wn_engine_predict_fold, chains._h,
+                   None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)),
+                   *(a.ctypes.data_as(_dp) for a in out), count.ctypes.data_as(_ffi._i64p))
+        return out + (count,)
+
+    def predict_chains(self, chains, block: int = 0, what: str = "mean"):
+        """The predictions of the k chains of dataset / weight set `block`, one value per draw and row, as MarkovChains
+        of their own on the device (wn_engine_predict_chains): `what` is "eta" (the linear predictor) or "mean"
+        (E[y | theta, x_n]); the result has one dimension per row and the source chains' lengths, so .quantiles(),
+        .r_hat(), .effective_sample_size() and the rest give credible bands and diagnostics of a prediction."""
+        codes = {"eta": 0, "mean": 1}
+        if what not in codes:
+            raise ValueError(f'what must be "eta" or "mean", got {what!r}')
+        h = C.c_void_p()
+        self._call(self.lib.wn_engine_predict_chains, chains._h, int(block), codes[what], C.byref(h))
+        return MarkovChains(h, self.lib)
 
     # ---- state
     def _get(self, fn, shape, dtype=np.float64, ptr=_dp):
