@@ -439,6 +439,36 @@ WALNUTS_HIP_EXPORT int wn_engine_predict_fold(wn_engine* e, wn_chains* chains, c
  * range; what outside {0, 1}.  A failed allocation is a `generic` error that states the bytes asked for. */
 WALNUTS_HIP_EXPORT int wn_engine_predict_chains(wn_engine* e, wn_chains* chains, int block, int what, wn_chains** out,
                                                 WalnutpyError** err);
+/* SIMULATED REPLICATES of a data model, y_rep ~ p(y | theta, x_n): what wn_engine_predict describes, drawn.  The
+ * samplers run per lane on the device on counter streams of their own (csrc/wn_devrand.h states the algorithms, the
+ * counter layout and their limits): a replicate depends on (seed, chain, draw, row) and on the row's mean and scale
+ * alone -- not on the launch, the mask or the other rows -- and the engine's own random streams are untouched.  Normal
+ * families draw a normal, the logistic ones a Bernoulli per trial (as wn_engine_predict), the Poisson ones a Poisson, the
+ * negative binomial a gamma-Poisson mixture.  A mean the samplers do not serve (non-finite, a Poisson mean above 2^30)
+ * gives NaN.  y and weights are never read.
+ * wn_engine_replicate: theta [T*D] in, out [T * rows of `dataset`] (host pointers); position t is drawn as chain t,
+ *   draw 0.  `config` errors: those of wn_engine_predict with the replicate hook (wn_model_api.h kReplicate) in place of
+ *   the predict hook. */
+WALNUTS_HIP_EXPORT int wn_engine_replicate(wn_engine* e, const double* theta, size_t num_theta, int dataset,
+                                           uint64_t seed, double* out, WalnutpyError** err);
+/* One replicate per draw and row, as chains of their own: *out owns a new device block [k][max_len][rows] -- chain c, draw
+ * i, row n holds y_rep of draw i of chain block * k + c, keyed by (seed, chain block * k + c, i, n) -- with the source
+ * chains' lengths; a predictive interval of an OBSERVATION is wn_summary_quantiles of it.  Arguments, errors and
+ * ownership as wn_engine_predict_chains. */
+WALNUTS_HIP_EXPORT int wn_engine_replicate_chains(wn_engine* e, wn_chains* chains, int block, uint64_t seed,
+                                                  wn_chains** out, WalnutpyError** err);
+/* POSTERIOR PREDICTIVE CHECKS folded where the draws live: for every draw of every chain, six statistics over the live
+ * rows (row_mask nonzero; NULL: every row) of the chain's dataset / weight set, of the replicate y_rep of that draw
+ * (stat_rep) and of the engine's observations y (stat_obs), each [6][chains][max_len] (host pointers; max_len = the
+ * longest chain; NaN beyond a chain's length):
+ *   0 sum q   1 sum q^2   2 min q   3 max q   4 #{q == 0}   5 sum (q - mu)^2 / v   (mu, v of wn_engine_predict)
+ * No [draws][rows] matrix exists at any time.  Weights are never applied.  Sums use rounded products in either
+ * arithmetic mode; csrc/wn_replicate.h states the order.  A draw with a non-finite live replicate has NaN in all six
+ * replicate statistics; with no live row the sums are 0, min = +inf and max = -inf.  The replicates are those of
+ * wn_engine_replicate_chains under the same seed.  row_mask is shaped as for wn_engine_predict_fold.  `config` errors:
+ * as wn_engine_predict_fold. */
+WALNUTS_HIP_EXPORT int wn_engine_replicate_check(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, uint64_t seed,
+                                                 double* stat_rep, double* stat_obs, WalnutpyError** err);
 
 /* InitConfig (config.hpp:74-185): positions [C*D], masses [C*D] (masses, not inverse
  * masses), step sizes [C]; host pointers. */
@@ -632,6 +662,14 @@ WALNUTS_HIP_EXPORT int wn_internal_math_probe(const double* x, const double* y, 
 WALNUTS_HIP_EXPORT int wn_internal_stream_probe(unsigned long long seed, unsigned int chain, unsigned int transition,
                                                 unsigned int stream, unsigned int first, size_t n, int normals, int tab,
                                                 double* out0, double* out1);
+/* ... the samplers of csrc/wn_devrand.h alone: argument i -- mu[i], shape[i] (the normal's sd, the gamma's shape, the
+ * negative binomial's kappa; both arrays hold n doubles) -- drawn on the counter stream of (seed, chain, draw, row0 + i).
+ * kind: 0 normal, 1 Bernoulli, 2 Poisson, 3 gamma, 4 negative binomial.  tab 0: ArrayTables, every lane on its own; tab
+ * 2: GatherTab, one argument per lane with all 64 lanes of a wavefront taking part in every loop (the last wavefront
+ * padded with copies of the last argument).  out[n] the samples, calls_out[n] the Philox calls each consumed. */
+WALNUTS_HIP_EXPORT int wn_internal_sampler_probe(int kind, const double* mu, const double* shape, unsigned long long seed,
+                                                 unsigned int chain, unsigned int draw, unsigned int row0, size_t n,
+                                                 int tab, double* out, int* calls_out);
 /* ... raw Philox4x32 with rounds = 7 or 10: counters ctr[4 n], keys key[2 n] -> out[4 n] */
 WALNUTS_HIP_EXPORT int wn_internal_philox_probe(const unsigned int* ctr, const unsigned int* key, unsigned int* out,
                                                 size_t n, int rounds);
@@ -668,6 +706,8 @@ WALNUTS_HIP_EXPORT size_t wn_chains_num_chains(const wn_chains* chains);
 WALNUTS_HIP_EXPORT size_t wn_chains_dims(const wn_chains* chains);
 WALNUTS_HIP_EXPORT size_t wn_chains_num_draws(const wn_chains* chains);
 WALNUTS_HIP_EXPORT size_t wn_chains_min_chain_size(const wn_chains* chains);
+/* the longest chain: max_len of the per-draw arrays of wn_engine_replicate_check */
+WALNUTS_HIP_EXPORT size_t wn_chains_max_chain_size(const wn_chains* chains);
 /* where the draws are: chain 0's first draw on device wn_chains_device() (chain c's n-th draw: see wn_chains_view) */
 WALNUTS_HIP_EXPORT const double* wn_chains_device_draws(const wn_chains* chains);
 WALNUTS_HIP_EXPORT int wn_chains_device(const wn_chains* chains);

@@ -17,3 +17,4 @@ from . import models, summary  # noqa: F401,E402
 from .summary import MarkovChains, Summarizer  # noqa: F401,E402
 from .pointwise import PointwisePredictive, kfold_elpd, log_predictive  # noqa: F401,E402
 from .predict import Prediction, predict, predict_draws  # noqa: F401,E402
+from .replicate import PredictiveCheck, posterior_predictive_check, replicate_draws  # noqa: F401,E402

@@ -102,6 +102,7 @@ SYMBOLS = [
     ("wn_internal_count_math_probe", _i32, [_dp, _dp, _dp, _sz, _i32]),
     ("wn_internal_math_probe", _i32, [_dp, _dp, _dp, _dp, _sz, _i32, _i32]),
     ("wn_internal_stream_probe", _i32, [_u64, _u32, _u32, _u32, _u32, _sz, _i32, _i32, _dp, _dp]),
+    ("wn_internal_sampler_probe", _i32, [_i32, _dp, _dp, _u64, _u32, _u32, _u32, _sz, _i32, _dp, _i32p]),
     ("wn_internal_philox_probe", _i32, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _sz, _i32]),
     ("wn_model_data_columns", _i32, [_i32, _i32, _i32]),
     ("wn_internal_reference_normals", None, [C.c_uint, C.c_uint, _sz, _sz, _i32, _dbl, _dp]),
@@ -129,6 +130,9 @@ SYMBOLS = [
     ("wn_engine_predict", _i32, [_vp, _dp, _sz, _i32, _dp, _dp, _dp, _errpp]),
     ("wn_engine_predict_fold", _i32, [_vp, _vp, C.POINTER(C.c_uint8), _dp, _dp, _dp, _dp, _dp, _i64p, _errpp]),
     ("wn_engine_predict_chains", _i32, [_vp, _vp, _i32, _i32, C.POINTER(_vp), _errpp]),
+    ("wn_engine_replicate", _i32, [_vp, _dp, _sz, _i32, _u64, _dp, _errpp]),
+    ("wn_engine_replicate_chains", _i32, [_vp, _vp, _i32, _u64, C.POINTER(_vp), _errpp]),
+    ("wn_engine_replicate_check", _i32, [_vp, _vp, C.POINTER(C.c_uint8), _u64, _dp, _dp, _errpp]),
     ("wn_engine_set_positions", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_set_masses", _i32, [_vp, _dp, _errpp]),
     ("wn_engine_set_step_sizes", _i32, [_vp, _dp, _errpp]),
@@ -199,6 +203,7 @@ SYMBOLS = [
     ("wn_chains_dims", _sz, [_vp]),
     ("wn_chains_num_draws", _sz, [_vp]),
     ("wn_chains_min_chain_size", _sz, [_vp]),
+    ("wn_chains_max_chain_size", _sz, [_vp]),
     ("wn_chains_device_draws", _vp, [_vp]),
     ("wn_chains_device", _i32, [_vp]),
     ("wn_summary_mean", _i32, [_vp, _dp, _errpp]),

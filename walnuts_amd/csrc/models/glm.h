@@ -49,6 +49,11 @@
 // n0 + k -- eta formed as pointwise() forms it (pointwise_eta, the offset), then ONE evaluation of Link::response on the
 // full wavefront: mu = E y and v = Var y given eta (wn_predict.h holds the table).  y and the weights are never read.
 //
+// The REPLICATE hook (wn_model_api.h, kReplicate; wn_replicate.h): replicate() forms (eta, mu, v) by the very expression
+// predict() uses and adds y_rep ~ p(y | theta, x_n), drawn by Link::replicate -- the sibling of response() -- ONCE on the
+// full wavefront from the lane's counter stream (wn_devrand.h: a normal with unit noise, a Bernoulli per trial, a
+// Poisson).  y and the weights are never read.
+//
 // Arithmetic: the prior variances arrive as reciprocals (host_params, as the diagonal normal's); the logistic mean is
 // one true division per block-row evaluation, 1 / (1 + exp(-|eta|)), and softplus(eta) = max(eta, 0) +
 // log(1 + exp(-|eta|)) never overflows.  exp / log are wnd::dexp / wnd::dlog with per-lane arguments (gather tables).
@@ -58,6 +63,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../wn_devrand.h"
 #include "../wn_model_api.h"
 
 namespace wn {
@@ -77,6 +83,11 @@ struct IdentityLink {
   __device__ __forceinline__ static void response(double eta, double& mu, double& v, const Tab&) {
     mu = eta;
     v = 1.0;
+  }
+  // y_rep ~ normal(mu, 1)
+  template <class Tab>
+  __device__ __forceinline__ static double replicate(double mu, RepStream& rng, const Tab& tab) {
+    return sample_normal(mu, 1.0, rng, tab);
   }
   static void check_y(double, bool) {}
   static long double pointwise_const(double) { return kHalfLog2Pi; }
@@ -101,6 +112,11 @@ struct LogitLink {
     const double d = 1.0 / (1.0 + e);
     mu = eta >= 0.0 ? d : e * d;
     v = (e * d) * d;
+  }
+  // y_rep ~ Bernoulli(mu), per trial
+  template <class Tab>
+  __device__ __forceinline__ static double replicate(double mu, RepStream& rng, const Tab&) {
+    return sample_bernoulli(mu, rng);
   }
   // (with weights y may be a proportion: k successes in m trials are weight m and y = k / m)
   static void check_y(double y, bool weighted) {
@@ -128,6 +144,11 @@ struct LogLink {
   __device__ __forceinline__ static void response(double eta, double& mu, double& v, const Tab& tab) {
     mu = wnd::dexp(eta, tab);
     v = mu;
+  }
+  // y_rep ~ Poisson(mu) (NaN where exp(eta) is not served: wn_devrand.h)
+  template <class Tab>
+  __device__ __forceinline__ static double replicate(double mu, RepStream& rng, const Tab& tab) {
+    return sample_poisson(mu, rng, tab, WaveAny{});
   }
   static void check_y(double y, bool) { check_count(y, "Poisson regression"); }
   static long double pointwise_const(double y) { return -lgammal(static_cast<long double>(y) + 1.0L); }
@@ -294,6 +315,15 @@ struct GlmModel {
     eta = pointwise_eta<EPL>(cx, th, n0, live, EPL / 2);
     if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n0 + opaque_lane_id()) : 0.0);
     Link::template response<Cx>(eta, mu, v, cx.gather_tab());
+  }
+
+  // the replicate hook (header comment): predict()'s triple and, from the lane's counter stream, y_rep of row n0 + k
+  static constexpr bool kReplicate = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void replicate(Cx& cx, const double (&th)[EPL], int n0, bool live, RepStream& rng,
+                                                   double& eta, double& mu, double& v, double& yrep) {
+    predict<EPL>(cx, th, n0, live, eta, mu, v);
+    yrep = Link::replicate(mu, rng, cx.gather_tab());
   }
 
   // host side: the prior variances -> their reciprocals (rounded once), and the observations' checks

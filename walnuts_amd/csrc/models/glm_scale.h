@@ -32,6 +32,10 @@
 // The predict hook (glm.h's header; wn_predict.h): glm.h's pointwise_eta and the offset, then the family's response on
 // the full wavefront with scale = exp(s) computed once per draw and tile: the negative binomial's mu = exp(eta),
 // v = mu + kappa mu^2 as Cx::mad(kappa * mu, mu, mu) with kappa = scale; the normal's mu = eta, v = scale * scale.
+//
+// The replicate hook (glm.h's header; wn_replicate.h): predict()'s triple, then the family's draw on the full wavefront
+// with the same scale: the negative binomial's gamma-Poisson mixture with kappa = scale, the normal's
+// fmad(scale, z, mu) -- scale itself, not sqrt(scale * scale).
 #pragma once
 
 #include "glm.h"
@@ -71,6 +75,11 @@ struct NegBinomialFamily {
     mu = wnd::dexp(eta, tab);
     v = Cx::mad(scale * mu, mu, mu);
   }
+  // y_rep ~ NB2(mu, kappa = scale)
+  template <class Tab>
+  __device__ __forceinline__ static double replicate(double mu, double scale, RepStream& rng, const Tab& tab) {
+    return sample_negbin(mu, scale, rng, tab, WaveAny{});
+  }
   static void check_y(double y, bool) { LogLink::check_count(y, "negative binomial regression"); }
   static long double pointwise_const(double y) { return LogLink::pointwise_const(y); }
 };
@@ -97,6 +106,11 @@ struct NormalSigmaFamily {
   __device__ __forceinline__ static void response(double eta, double scale, double& mu, double& v, const Tab&) {
     mu = eta;
     v = scale * scale;
+  }
+  // y_rep ~ normal(mu, sigma = scale)
+  template <class Tab>
+  __device__ __forceinline__ static double replicate(double mu, double scale, RepStream& rng, const Tab& tab) {
+    return sample_normal(mu, scale, rng, tab);
   }
   static void check_y(double, bool) {}
   static long double pointwise_const(double) { return kHalfLog2Pi; }
@@ -225,6 +239,16 @@ struct GlmScaleModel {
     eta = pointwise_eta<EPL>(cx, th, n0, live, EPL / 2);
     if (cx.has_offset()) eta = eta + (live ? cx.obs_offset(n0 + opaque_lane_id()) : 0.0);
     Family::template response<Cx>(eta, scale, mu, v, cx.gather_tab());
+  }
+
+  // the replicate hook (header comment): predict()'s triple and y_rep of row n0 + k
+  static constexpr bool kReplicate = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void replicate(Cx& cx, const double (&th)[EPL], int n0, bool live, RepStream& rng,
+                                                   double& eta, double& mu, double& v, double& yrep) {
+    predict<EPL>(cx, th, n0, live, eta, mu, v);
+    const double scale = wnd::dexp(coord_value(th, cx.dim() - 1), cx.uniform_tab());  // (predict()'s own, again)
+    yrep = Family::replicate(mu, scale, rng, cx.gather_tab());
   }
 
   // host side: the beta prior variances -> reciprocals, sigma_0 -> 1 / sigma_0^2 (each rounded once); the

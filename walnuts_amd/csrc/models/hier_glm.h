@@ -230,6 +230,15 @@ struct HierGlmModel {
     Link::template response<Cx>(eta, mu, v, cx.gather_tab());
   }
 
+  // the replicate hook (glm.h's header; wn_replicate.h): predict()'s triple and y_rep of row n0 + k
+  static constexpr bool kReplicate = true;
+  template <int EPL, class Cx>
+  __device__ __forceinline__ static void replicate(Cx& cx, const double (&th)[EPL], int n0, bool live, RepStream& rng,
+                                                   double& eta, double& mu, double& v, double& yrep) {
+    predict<EPL>(cx, th, n0, live, eta, mu, v);
+    yrep = Link::replicate(mu, rng, cx.gather_tab());
+  }
+
   // host side: the beta prior variances and the reserved entries -> reciprocals, sigma_tau -> 1 / sigma_tau^2 (each
   // rounded once); the observations' checks are the link's
   static void host_params(double* mp, int num_params) {

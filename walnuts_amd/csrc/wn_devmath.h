@@ -503,7 +503,9 @@ WND_HD U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0
   return U4{c0, c1, c2, c3};
 }
 
-enum : uint32_t { kStreamMomentum = 0, kStreamTree = 1, kStreamInitPos = 2, kStreamInitStep = 3 };
+// (kStreamReplicate: the simulated replicates of wn_devrand.h, whose counter layout is stated there; adding it leaves
+// the streams 0-3, and so kStreamVersion, as they were)
+enum : uint32_t { kStreamMomentum = 0, kStreamTree = 1, kStreamInitPos = 2, kStreamInitStep = 3, kStreamReplicate = 4 };
 
 WND_HD double dpow_pos(double x, double y) { return dpow_pos(x, y, array_tables()); }
 

@@ -10,6 +10,7 @@
 #include "wn_launch.h"
 #include "wn_pointwise.h"
 #include "wn_predict.h"
+#include "wn_replicate.h"
 #include "wn_traj.h"
 
 #define WN_CAT2(a, b) a##b
@@ -34,6 +35,9 @@ static_assert(!kPointwise || kUsesData, "kPointwise needs kUsesData (wn_model_ap
 // ... and the prediction kernels (wn_predict.h)
 static constexpr bool kPredict = is_predict<WN_MODEL_TYPE>::value;
 static_assert(!kPredict || kUsesData, "kPredict needs kUsesData (wn_model_api.h)");
+// ... and the replicate kernels (wn_replicate.h)
+static constexpr bool kReplicate = is_replicate<WN_MODEL_TYPE>::value;
+static_assert(!kReplicate || kPredict, "kReplicate needs kPredict (wn_model_api.h)");
 
 void WN_CAT(launch_transition_, WN_MODEL_TAG)(const Geometry& g, int grid, size_t smem, hipStream_t stream,
                                                const Params& p) {
@@ -233,6 +237,39 @@ void WN_CAT(launch_predict_combine_, WN_MODEL_TAG)(int grid, hipStream_t stream,
 static const PredictOps WN_CAT(kPredictOps_, WN_MODEL_TAG) = {&WN_CAT(launch_predict_, WN_MODEL_TAG),
                                                               &WN_CAT(launch_predict_combine_, WN_MODEL_TAG)};
 
+// wn_engine_replicate / wn_engine_replicate_chains / wn_engine_replicate_check: one wavefront per work item, the engine's
+// elements per lane and arithmetic mode (replicate_kernel, wn_replicate.h).  Instantiated for a model that declares the
+// hook only.
+namespace {
+template <class M, bool kOn = is_replicate<M>::value>
+struct ReplicateLaunch {
+  static void launch(const Geometry&, int, hipStream_t, bool, const ReplicateParams&) {}
+};
+template <class M>
+struct ReplicateLaunch<M, true> {
+  static void launch(const Geometry& g, int grid, hipStream_t stream, bool fma, const ReplicateParams& q) {
+#define WN_X(NW, EPL)                                                                            \
+  if constexpr (NW == 1) {                                                                       \
+    if (!g.mem && g.nw == 1 && g.epl == EPL) {                                                   \
+      if (fma)                                                                                   \
+        hipLaunchKernelGGL((replicate_kernel<M, EPL, true>), dim3(grid), dim3(64), 0, stream, q);  \
+      else                                                                                       \
+        hipLaunchKernelGGL((replicate_kernel<M, EPL, false>), dim3(grid), dim3(64), 0, stream, q); \
+      return;                                                                                    \
+    }                                                                                            \
+  }
+    WN_FOR_EACH_GEOMETRY(WN_X)
+#undef WN_X
+    throw std::invalid_argument("no replicate kernel for this geometry");
+  }
+};
+}  // namespace
+void WN_CAT(launch_replicate_, WN_MODEL_TAG)(const Geometry& g, int grid, hipStream_t stream, bool fma,
+                                              const ReplicateParams& q) {
+  ReplicateLaunch<WN_MODEL_TYPE>::launch(g, grid, stream, fma, q);
+}
+static const ReplicateOps WN_CAT(kReplicateOps_, WN_MODEL_TAG) = {&WN_CAT(launch_replicate_, WN_MODEL_TAG)};
+
 void WN_CAT(prepare_, WN_MODEL_TAG)(const Geometry& g, size_t smem) {
   if (g.mem) {
     if constexpr (!kHasStreaming) {
@@ -360,7 +397,8 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     scale_param<WN_MODEL_TYPE>::value,
     uses_row_terms<WN_MODEL_TYPE>::value,
     kPointwise ? &WN_CAT(kPointwiseOps_, WN_MODEL_TAG) : nullptr,
-    kPredict ? &WN_CAT(kPredictOps_, WN_MODEL_TAG) : nullptr};
+    kPredict ? &WN_CAT(kPredictOps_, WN_MODEL_TAG) : nullptr,
+    kReplicate ? &WN_CAT(kReplicateOps_, WN_MODEL_TAG) : nullptr};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

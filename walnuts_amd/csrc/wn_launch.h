@@ -15,6 +15,7 @@ struct InitParams;
 struct PointwiseParams;
 struct PointwiseCombineParams;
 struct PredictParams;
+struct ReplicateParams;
 struct PredictCombineParams;
 
 // NW wavefronts cooperate on one chain, each lane holds EPL elements of every vector:
@@ -187,6 +188,11 @@ struct PredictOps {
   // the across-chain merge of the fold (predict_combine_kernel)
   void (*launch_combine)(int grid, hipStream_t, const PredictCombineParams&);
 };
+// The simulated replicates of a data model that declares the hook (wn_model_api.h, kReplicate; wn_replicate.h)
+struct ReplicateOps {
+  // the matrix, the generated chains and the per-draw check (replicate_kernel), one wavefront per work item
+  void (*launch)(const Geometry&, int grid, hipStream_t, bool fma, const ReplicateParams&);
+};
 struct ModelOps {
   int id;
   const char* name;
@@ -213,6 +219,7 @@ struct ModelOps {
   bool uses_row_terms;  // a data model that reads per-row offsets and weights (kUsesRowTerms)
   const PointwiseOps* pointwise;  // the pointwise log-likelihood (kPointwise); null: the model declares no such hook
   const PredictOps* predict;      // eta, mean and variance of a row (kPredict); null: the model declares no such hook
+  const ReplicateOps* replicate;  // simulated replicates of a row (kReplicate); null: the model declares no such hook
 };
 constexpr int kMaxModels = 64;
 inline const ModelOps** model_table() {
@@ -227,7 +234,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 15;
+constexpr int kModelAbiVersion = 16;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

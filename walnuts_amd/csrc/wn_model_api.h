@@ -103,6 +103,20 @@
 //     static constexpr bool kPredict = true;
 //     template <int EPL, class Cx>
 //     static void predict(Cx& cx, const double (&theta)[EPL], int n0, bool live, double& eta, double& mu, double& v);
+//     // ... and, on top of kPredict, SIMULATED REPLICATES (wn_replicate.h: wn_engine_replicate,
+//     // wn_engine_replicate_chains, wn_engine_replicate_check -- y_rep ~ p(y | theta, x_n) and posterior predictive
+//     // checks from draws that stay on the device).  replicate() leaves, in lane k, predict()'s triple of row n0 + k --
+//     // formed by the very expression predict() uses -- and yrep, ONE draw from the row's distribution taken from `rng`,
+//     // the lane's counter stream (wn::RepStream, wn_devrand.h: keyed by seed, row, draw and chain; the kernel sets it
+//     // up, the model only draws).  The built-in models call Link::replicate / Family::replicate, the sibling of
+//     // response(), once on the full wavefront: wn::sample_normal / sample_bernoulli / sample_poisson / sample_negbin.
+//     // A sampler with a loop must keep the wavefront together (wn::WaveAny; wn_devrand.h says why); y and the weights
+//     // are never read.  An engine whose model lacks this member refuses the three entry points with a `config`
+//     // error that names the model.
+//     static constexpr bool kReplicate = true;
+//     template <int EPL, class Cx>
+//     static void replicate(Cx& cx, const double (&theta)[EPL], int n0, bool live, wn::RepStream& rng, double& eta,
+//                           double& mu, double& v, double& yrep);
 //   };
 //
 // What `cx` offers (all of it collective: every lane of the chain's workgroup must make the same calls):
@@ -135,7 +149,7 @@
 //   cx.obs_offset(n), cx.obs_weight(n)        offset_n / weight_n (0 <= n < num_obs; only where has_*() is true) -- with
 //                                             weight sets, of the set the chain is conditioned on; the model cannot tell
 // (pointwise() receives the same calls over the block of rows being scored -- wn_pointwise.h, PointwiseCx -- with
-// cx.has_weight() false; cx.sum1 / element0 / shift are not offered there; predict() receives the same cx)
+// cx.has_weight() false; cx.sum1 / element0 / shift are not offered there; predict() and replicate() receive the same cx)
 // The wavefront primitives of the platform layer (wave_sum_packed, lane_value, set_lane, uni, ...: wn_gfx950.h, with
 // the same association order under the CPU emulation) are available to eval(); models/glm.h uses them to reduce two
 // rows' dot products per butterfly.

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "../../include/walnuts_hip.h"
+#include "wn_devrand.h"
 #include "wn_traj.h"
 
 #include "wn_host.h"
@@ -107,6 +108,60 @@ static __global__ void math_probe_kernel(MathProbeArgs A) {
           A.o0[i] = r0;
           if (two) A.o1[i] = r1;
         }
+      }
+    }
+  }
+}
+// (internal, for the tests) the samplers of wn_devrand.h alone: argument i (mu[i], shape[i]) is drawn on the counter
+// stream of (row0 + i, draw, chain).  `tab` 0: ArrayTables, one argument per thread, every loop the lane's own (LaneAny);
+// 2: GatherTab, one argument per lane, ALL 64 lanes of a wavefront take part in every loop (WaveAny): a last, partial
+// wavefront runs with clamped indices -- copies of the last argument on its row -- and masks only its store.  kind:
+// wn::kSample*.  shape: the normal's sd, the gamma's shape, the negative binomial's kappa; unread otherwise.
+struct SamplerProbeArgs {
+  const double* mu;
+  const double* shape;
+  double* out;
+  int* calls;
+  long long n;
+  int kind;
+  unsigned long long seed;
+  uint32_t chain, draw, row0;
+};
+template <class Tab, class Any>
+static __device__ __forceinline__ double sampler_probe_eval(int kind, double mu, double shape, wn::RepStream& s,
+                                                            const Tab& tab, const Any& any) {
+  switch (kind) {   // (wave-uniform)
+    case wn::kSampleNormal: return wn::sample_normal(mu, shape, s, tab);
+    case wn::kSampleBernoulli: return wn::sample_bernoulli(mu, s);
+    case wn::kSamplePoisson: return wn::sample_poisson(mu, s, tab, any);
+    case wn::kSampleGamma: return wn::sample_gamma(shape, s, tab, any);
+    default: return wn::sample_negbin(mu, shape, s, tab, any);
+  }
+}
+template <int TAB>
+static __global__ void sampler_probe_kernel(SamplerProbeArgs A) {
+  const long long thread = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
+  const long long threads = static_cast<long long>(gridDim.x) * blockDim.x;
+  if constexpr (TAB == 0) {
+    const wnd::ArrayTables tab = wnd::array_tables();
+    for (long long i = thread; i < A.n; i += threads) {
+      wn::RepStream s{A.seed, A.row0 + static_cast<uint32_t>(i), A.draw, A.chain, 0u};
+      A.out[i] = sampler_probe_eval(A.kind, A.mu[i], A.shape[i], s, tab, wn::LaneAny{});
+      A.calls[i] = static_cast<int>(s.call);
+    }
+  } else {
+    const int lane = wn::opaque_lane_id();
+    wn::LaneTables tabs;
+    tabs.load(lane);
+    const wn::GatherTab tab{tabs};
+    const long long wave = thread >> 6, waves = threads >> 6;
+    for (long long base = wave * 64; base < A.n; base += waves * 64) {   // (the bound is wave-uniform)
+      const long long i = base + lane, ic = i < A.n ? i : A.n - 1;
+      wn::RepStream s{A.seed, A.row0 + static_cast<uint32_t>(ic), A.draw, A.chain, 0u};
+      const double y = sampler_probe_eval(A.kind, A.mu[ic], A.shape[ic], s, tab, wn::WaveAny{});
+      if (i < A.n) {
+        A.out[i] = y;
+        A.calls[i] = static_cast<int>(s.call);
       }
     }
   }
@@ -226,6 +281,39 @@ int wn_internal_stream_probe(unsigned long long seed, unsigned int chain, unsign
   A.stream = stream;
   A.first = first;
   return run_math_probe(A, nullptr, nullptr, out0, out1, tab);
+}
+
+int wn_internal_sampler_probe(int kind, const double* mu, const double* shape, unsigned long long seed, unsigned int chain,
+                               unsigned int draw, unsigned int row0, size_t n, int tab, double* out, int* calls_out) {
+  if (kind < 0 || kind > wn::kSampleNegBin || (tab != 0 && tab != 2) || mu == nullptr || shape == nullptr ||
+      out == nullptr || calls_out == nullptr || static_cast<unsigned long long>(row0) + n > 0x100000000ULL)
+    return -2;
+  if (n == 0) return 0;
+  DevBuf<double> dm, ds, dout;
+  DevBuf<int> dcalls;
+  try {
+    dm.alloc(n);
+    ds.alloc(n);
+    dout.alloc(n);
+    dcalls.alloc(n);
+    HIP_OK(hipMemcpyAsync(dm.p, mu, n * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    HIP_OK(hipMemcpyAsync(ds.p, shape, n * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    SamplerProbeArgs A{dm.p, ds.p, dout.p, dcalls.p, static_cast<long long>(n), kind, seed, chain, draw, row0};
+    // whole wavefronts, and no more of them than there is work
+    const dim3 grid(static_cast<unsigned>(std::min<size_t>(1024, (n + 255) / 256))), block(256);
+    if (tab == 0) {
+      hipLaunchKernelGGL(sampler_probe_kernel<0>, grid, block, 0, nullptr, A);
+    } else {
+      hipLaunchKernelGGL(sampler_probe_kernel<2>, grid, block, 0, nullptr, A);
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIP_OK(hipMemcpyAsync(calls_out, dcalls.p, n * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    HIP_OK(hipStreamSynchronize(nullptr));
+  } catch (...) {
+    return -1;
+  }
+  return 0;
 }
 
 int wn_internal_philox_probe(const unsigned int* ctr, const unsigned int* key, unsigned int* out, size_t n, int rounds) {

@@ -776,6 +776,7 @@ size_t wn_chains_num_chains(const wn_chains* ch) { return ch->C; }
 size_t wn_chains_dims(const wn_chains* ch) { return ch->D; }
 size_t wn_chains_num_draws(const wn_chains* ch) { return static_cast<size_t>(ch->N); }
 size_t wn_chains_min_chain_size(const wn_chains* ch) { return static_cast<size_t>(ch->min_len); }
+size_t wn_chains_max_chain_size(const wn_chains* ch) { return static_cast<size_t>(ch->max_len); }
 const double* wn_chains_device_draws(const wn_chains* ch) { return ch->x; }
 int wn_chains_device(const wn_chains* ch) { return ch->device; }
 

@@ -292,6 +292,40 @@ class DeviceEngine:
         self._call(self.lib.wn_engine_predict_chains, chains._h, int(block), codes[what], C.byref(h))
         return MarkovChains(h, self.lib)
 
+    def replicate(self, theta, seed: int, dataset: int = 0):
+        """Simulated replicates y_rep [T, N] ~ p(y | theta[t], x_n) of every row of dataset `dataset` (wn_engine_replicate):
+        what predict() describes, drawn on the device from counter streams keyed by (seed, t, row) -- position t is
+        chain t, draw 0 of replicate_chains' layout.  The engine's own random streams and chain state are untouched."""
+        th = _f64(theta).reshape(-1, self.D)
+        out = np.empty((th.shape[0], self._rows(int(dataset))))
+        self._call(self.lib.wn_engine_replicate, th.ctypes.data_as(_dp), th.shape[0], int(dataset), int(seed),
+                   out.ctypes.data_as(_dp))
+        return out
+
+    def replicate_chains(self, chains, seed: int, block: int = 0):
+        """One replicate per draw and row of the k chains of dataset / weight set `block`, as MarkovChains of their own on
+        the device (wn_engine_replicate_chains): .quantiles() is a predictive interval of an OBSERVATION."""
+        h = C.c_void_p()
+        self._call(self.lib.wn_engine_replicate_chains, chains._h, int(block), int(seed), C.byref(h))
+        return MarkovChains(h, self.lib)
+
+    def replicate_check(self, chains, seed: int, row_mask=None):
+        """(stat_rep, stat_obs), each [6, chains, max_len]: per draw the statistics sum, sum of squares, min, max, number
+        of zeros and Pearson discrepancy over the live rows, of the draw's replicate and of the engine's observations
+        (wn_engine_replicate_check); NaN beyond a chain's length.  `row_mask` as for predict_fold.
+        walnuts_amd.posterior_predictive_check wraps this."""
+        shape = self._rows() if not self._weight_sets else (self.num_datasets, self._row_sizes[0])
+        mask = None
+        if row_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(row_mask) != 0, dtype=np.uint8)
+            if mask.shape != tuple(shape):
+                raise ValueError(f"row_mask must have shape {tuple(shape)}, got {mask.shape}")
+        out = tuple(np.full((6, chains.num_chains(), chains.max_chain_size()), np.nan) for _ in range(2))
+        self._call(self.lib.wn_engine_replicate_check, chains._h,
+                   None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), int(seed),
+                   *(a.ctypes.data_as(_dp) for a in out))
+        return out
+
     # ---- state
     def _get(self, fn, shape, dtype=np.float64, ptr=_dp):
         out = np.empty(shape, dtype=dtype)

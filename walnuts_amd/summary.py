@@ -102,6 +102,9 @@ class MarkovChains:
     def min_chain_size(self) -> int:
         return int(self.lib.wn_chains_min_chain_size(self._h))
 
+    def max_chain_size(self) -> int:
+        return int(self.lib.wn_chains_max_chain_size(self._h))
+
     def close(self):
         if self._h:
             self.lib.wn_chains_destroy(self._h)
