@@ -153,7 +153,13 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
  * sigma = exp(s)), which end theta with the log scale s and take model_params [prior variances (num_params - 1) |
  * sigma_0], the half-normal scale of exp(s); P = num_params - num_groups - 1 (P >= 1, num_groups >= 1) for a GROUPED
  * model (kUsesGroups: the hier_* models and their _centered forms, walnuts_amd/csrc/models/hier_glm.h), which also reads
- * `group`.  The count models refuse a y that is not a finite non-negative integer (`config`).
+ * `group`.  VARYING SLOPES (kVaryingSlopes: hier_linear_regression_slopes 32, hier_logistic_regression_slopes 33,
+ * hier_poisson_regression_slopes 34, walnuts_amd/csrc/models/hier_slopes_glm.h): num_varying = Q coefficients vary by
+ * group, the intercept and the slopes of the FIRST Q - 1 columns of x, with independent scales; theta = [beta (P) |
+ * u_0 (num_groups) | .. | u_{Q-1} (num_groups) | s_0 .. s_{Q-1}], model_params = [prior variances (P) | 1 (Q num_groups,
+ * reserved) | sigma_0 .. sigma_{Q-1}], P = num_params - Q (num_groups + 1) =
+ * wn_model_data_columns_varying(model, num_params, num_groups, num_varying); at Q = 1 such a model is its hier_* sibling,
+ * bit for bit.  The count models refuse a y that is not a finite non-negative integer (`config`).
  * MANY datasets at once (one model, one prior): with obs_offsets != NULL, dataset g is rows [obs_offsets[g],
  * obs_offsets[g + 1]) of x, y and group (from 0, strictly increasing; datasets may differ in size; num_groups is shared
  * and a dataset may leave groups empty), and chain c is conditioned on dataset c / k, k = num_chains / num_datasets
@@ -180,6 +186,7 @@ typedef struct wn_observations {
   const double* offset;       /* [rows]; NULL: none */
   const double* weight;       /* [rows], or [num_weight_sets][num_obs]; NULL: every weight 1 */
   int num_weight_sets;        /* 0 or 1: one weight vector; W > 1: weight sets */
+  int num_varying;            /* 0 or 1: the intercept alone varies by group; Q > 1: varying slopes (models with kVaryingSlopes) */
 } wn_observations;
 
 /* walnutpie_sample_device / _resident for a model conditioned on data: `obs` after num_params, everything else as the
@@ -326,6 +333,11 @@ WALNUTS_HIP_EXPORT int wn_model_id(const char* name);
  * linear_regression_sigma), num_params - num_groups - 1 for a grouped model.  -> -1 for an id no data model holds, and
  * for a grouped model with num_groups < 1. */
 WALNUTS_HIP_EXPORT int wn_model_data_columns(int model, int num_params, int num_groups);
+/* The same with num_varying (wn_observations): num_params - Q (num_groups + 1) for a model with varying slopes, Q =
+ * num_varying (0 meaning 1); for every other model wn_model_data_columns' answer when num_varying <= 1.  -> -1 where
+ * wn_engine_create_observed would refuse the numbers: num_varying > 1 for a model without varying slopes, Q outside
+ * [1, 8], num_groups < 1, fewer than one column, or Q - 1 above the number of columns. */
+WALNUTS_HIP_EXPORT int wn_model_data_columns_varying(int model, int num_params, int num_groups, int num_varying);
 /* Version of the counter-based random streams of this build (the map (seed, chain, transition, index) -> variate,
  * csrc/wn_devmath.h): results at a fixed seed are reproducible within one version only.  A caller that stores draws
  * or resumes a run records it beside the seed; walnuts_amd writes it into every result and bench line.
@@ -372,7 +384,9 @@ WALNUTS_HIP_EXPORT int wn_engine_create(wn_engine** out, int model, int num_para
  * seeded with chain_offset = g * k; the pooled statistics below keep their meaning (all chains), the _datasets ones are
  * per dataset.  `config` errors: obs == NULL; a data model created through wn_engine_create; data for a model without
  * kUsesData; a grouped model without `group`, and `group` for a model without kUsesGroups; num_params != P + num_groups
- * + 1 with P >= 1 and num_groups >= 1; num_datasets < 1, num_chains not a multiple of it, offsets not from 0 or not
+ * + 1 with P >= 1 and num_groups >= 1; num_varying > 1 for a model without kVaryingSlopes, and for a model with it
+ * num_varying outside [0, 8], num_params != P + Q (num_groups + 1) with P >= 1 and num_groups >= 1, or Q - 1 > P (Q =
+ * num_varying, 0 meaning 1; the messages name the numbers); num_datasets < 1, num_chains not a multiple of it, offsets not from 0 or not
  * strictly increasing; non-finite data; a group outside [0, num_groups); a non-finite offset; a weight that is negative
  * or not finite; offsets or weights for a model without kUsesRowTerms; num_weight_sets < 0, > 1 without `weight`, > 1
  * together with obs_offsets, or not dividing num_chains (all checked before anything is uploaded); the model's own

@@ -19,10 +19,12 @@ def _is_grouped(data) -> bool:
         return False
 
 
-def _block(data, num_params: int, cols: int):
+def _block(data, num_params: int, cols: int, varying: int = 1):
     """One block of observations as contiguous arrays (x, y, group, J).  A pair (x, y): x (num_obs, cols) float64, y
     (num_obs,) float64, group None, J 0.  A triple (x, y, group) of a grouped model (kUsesGroups): x (num_obs, P), group
-    (num_obs,) int32 and J = num_params - P - 1 (the engine checks J >= 1, P >= 1 and the range)."""
+    (num_obs,) int32 and J = (num_params - P) / varying - 1, varying = Q the number of coefficients that vary by group
+    (kVaryingSlopes; 1: J = num_params - P - 1); a remainder is refused here, and the engine checks J >= 1, P >= 1,
+    Q - 1 <= P and the range."""
     grouped = _is_grouped(data)
     if grouped:
         x, y, group = data
@@ -49,10 +51,14 @@ def _block(data, num_params: int, cols: int):
         raise ValueError(f"data group must hold integers, got dtype {g.dtype}")
     if g.size and (g.min() < np.iinfo(np.int32).min or g.max() > np.iinfo(np.int32).max):
         raise ValueError("every group must be in [0, num_groups)")
-    return x, y, np.ascontiguousarray(g, dtype=np.int32), num_params - x.shape[1] - 1
+    rest = num_params - x.shape[1]
+    if rest % varying != 0:
+        raise ValueError(f"num_params - P must be a multiple of varying (num_params == P + varying * (J + 1)), got "
+                         f"num_params {num_params}, P {x.shape[1]}, varying {varying}")
+    return x, y, np.ascontiguousarray(g, dtype=np.int32), rest // varying - 1
 
 
-def _blocks(datasets, num_params: int, cols: int):
+def _blocks(datasets, num_params: int, cols: int, varying: int = 1):
     """Several datasets [(x0, y0), ...] or [(x0, y0, group0), ...] as one block, stacked in order: (x, y, group, J) as
     _block gives them, and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1])."""
     try:
@@ -65,7 +71,7 @@ def _blocks(datasets, num_params: int, cols: int):
     if any(_is_grouped(d) != grouped for d in items):
         raise ValueError("datasets must be all (x, y) pairs or all (x, y, group) triples")
     try:
-        parts = [_block(d, num_params, cols) for d in items]
+        parts = [_block(d, num_params, cols, varying) for d in items]
     except TypeError:
         if grouped:
             raise
@@ -110,12 +116,16 @@ def _row_terms(name: str, value, sizes, several: bool):
 
 
 def observations(lib, model: int, num_params: int, data=None, datasets=None, offset=None, weights=None,
-                 weight_sets=None):
+                 weight_sets=None, varying: int = 1):
     """The wn_observations of `data=(x, y[, group])` or `datasets=[(x0, y0[, group0]), ...]`, or None without either,
     with the per-row `offset=` and `weights=` (one array, or one per dataset) and `weight_sets=` ((W, num_obs), with
-    `data=` only).  The struct keeps the arrays it points into alive (`.arrays`); pass it with ctypes.byref."""
+    `data=` only) and `varying=` (Q >= 1 coefficients that vary by group, for a model with kVaryingSlopes: it says how
+    num_params splits into P, J and Q, and travels as wn_observations::num_varying).  The struct keeps the arrays it points into alive (`.arrays`); pass it with ctypes.byref."""
     if data is not None and datasets is not None:
         raise ValueError("data and datasets are mutually exclusive")
+    varying = int(varying)
+    if varying < 1:
+        raise ValueError(f"varying must be at least 1 (the intercept), got {varying}")
     if data is None and datasets is None:
         if offset is not None or weights is not None or weight_sets is not None:
             raise ValueError("offset, weights and weight_sets need data or datasets")
@@ -131,12 +141,13 @@ def observations(lib, model: int, num_params: int, data=None, datasets=None, off
     cols = cols if cols >= 0 else int(num_params)
     obs = _ffi.Observations()
     if datasets is not None:
-        x, y, group, J, offsets = _blocks(datasets, num_params, cols)
+        x, y, group, J, offsets = _blocks(datasets, num_params, cols, varying)
         obs.obs_offsets, obs.num_datasets = offsets.ctypes.data_as(_ffi._i64p), offsets.size - 1
     else:
-        x, y, group, J = _block(data, num_params, cols)
+        x, y, group, J = _block(data, num_params, cols, varying)
         offsets = None
         obs.num_obs = y.size
+    obs.num_varying = varying   # (the engine refuses varying > 1 for a model without varying slopes)
     obs.x, obs.y = x.ctypes.data_as(_ffi._dp), y.ctypes.data_as(_ffi._dp)
     if group is not None:
         obs.group, obs.num_groups = group.ctypes.data_as(_ffi._i32p), J

@@ -96,7 +96,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   static constexpr int kOther = -4;           // "this vector is the other end's theta" (kOtherRegs)
   Parked oth[EPL], orh[EPL];
   int n_lds;                                  // pool buffers [0, n_lds) live in LDS, the rest in the HBM arena
-  const double* obs_x = nullptr;              // data models: the bound chain's observations (bind_data)
+  const double* obs_xv = nullptr;              // data models: the bound chain's observations (bind_data)
   const double* obs_yv = nullptr;
   const int32_t* obs_gv = nullptr;            // grouped data models: the bound chain's group indices
   const double* obs_ov = nullptr;             // kUsesRowTerms: the bound chain's offsets and weights (null: absent)
@@ -132,7 +132,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
       // rows of P = num_params - num_groups - 1 columns at stride Dx = obs.stride = 128 * ceil(P / 128): slot pair k
       // holds columns [128 k, 128 k + 128), so pairs k >= Dx / 128 are zeros and issue no load (a wave-uniform test)
       const int nx = P.obs.stride / (2 * L);
-      const char* lb = lane_base(obs_x + static_cast<long long>(n) * P.obs.stride);
+      const char* lb = lane_base(obs_xv + static_cast<long long>(n) * P.obs.stride);
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
         if (k < nx) {
@@ -145,13 +145,19 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
         }
       }
     } else {
-      vload(obs_x + static_cast<long long>(n) * kDp, x);
+      vload(obs_xv + static_cast<long long>(n) * kDp, x);
     }
   }
   __device__ __forceinline__ double obs_y(int n) const { return obs_yv[n]; }
   // grouped data models (kUsesGroups): J, wave-uniform, and the group of observation n, in [0, J)
   __device__ __forceinline__ int num_groups() const { return P.obs.num_groups; }
   __device__ __forceinline__ int obs_group(int n) const { return obs_gv[n]; }
+  // ... with varying slopes (kVaryingSlopes): Q >= 1 coefficients vary by group, wave-uniform, and column `col` of row
+  // n of x, a per-lane load (a row laid out like theta is its columns in order; col below the row's stride)
+  __device__ __forceinline__ int num_varying() const { return P.obs.num_varying; }
+  __device__ __forceinline__ double obs_x(int n, int col) const {
+    return obs_xv[static_cast<long long>(n) * (uses_groups<Model>::value ? static_cast<long long>(P.obs.stride) : kDp) + col];
+  }
   // data models that read per-row offsets and weights (kUsesRowTerms): whether the engine holds them (wave-uniform),
   // and observation n's (only where has_*() is true)
   __device__ __forceinline__ bool has_offset() const { return obs_ov != nullptr; }
@@ -166,7 +172,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
   __device__ __forceinline__ void bind_data(int c) {
     if constexpr (uses_data<Model>::value) {
       if (P.obs.chains_per_dataset > 0 && P.obs.offsets == nullptr) {
-        obs_x = P.obs.x;
+        obs_xv = P.obs.x;
         obs_yv = P.obs.y;
         if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group;
         obs_n = P.obs.num_obs;
@@ -178,7 +184,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
       } else if (P.obs.chains_per_dataset > 0) {
         const int ds = c / P.obs.chains_per_dataset;
         const long long first = P.obs.offsets[ds];
-        obs_x = P.obs.x + first * (uses_groups<Model>::value ? static_cast<long long>(P.obs.stride) : kDp);
+        obs_xv = P.obs.x + first * (uses_groups<Model>::value ? static_cast<long long>(P.obs.stride) : kDp);
         obs_yv = P.obs.y + first;
         if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group + first;
         obs_n = static_cast<int>(P.obs.offsets[ds + 1] - first);
@@ -187,7 +193,7 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
           obs_wv = P.obs.weight != nullptr ? P.obs.weight + first : nullptr;
         }
       } else {
-        obs_x = P.obs.x;
+        obs_xv = P.obs.x;
         obs_yv = P.obs.y;
         if constexpr (uses_groups<Model>::value) obs_gv = P.obs.group;
         obs_n = P.obs.num_obs;

@@ -35,6 +35,9 @@ void check_model_inputs(const wn::ModelOps& ops, int num_params, const double* m
                                 "[num_obs] in [0, num_groups))");
   if (!ops.uses_groups && data != nullptr && data->group != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
+  if (ops.host_params_varying == nullptr && data != nullptr && data->num_varying > 1)
+    throw std::invalid_argument(std::string(ops.name) + " model has no varying slopes (it does not declare kVaryingSlopes): "
+                                "num_varying must be 0 or 1, got " + std::to_string(data->num_varying));
   if (!ops.uses_row_terms && data != nullptr && (data->offset != nullptr || data->weight != nullptr))
     throw std::invalid_argument(std::string(ops.name) + " model reads no offsets or weights (it does not declare "
                                 "kUsesRowTerms)");
@@ -43,7 +46,8 @@ void check_model_inputs(const wn::ModelOps& ops, int num_params, const double* m
 // The shape of a checked observation block, as the upload and the monitors need it (all defaults without data)
 struct ObservationPlan {
   int cols = 0;          // columns of x: num_params, num_params - 1 for a model with a scale parameter, or
-                         // P = num_params - J - 1 for a grouped model
+                         // P = num_params - Q (J + 1) for a grouped model
+  int num_varying = 0;   // Q of a grouped model: coefficients that vary by group (1 without kVaryingSlopes)
   size_t total_obs = 0;  // rows of the observation block
   int weight_sets = 1;   // W weight vectors over the one shared block, an engine of W datasets above the kernels
   bool weighted = false;
@@ -112,12 +116,29 @@ ObservationPlan plan_observations(const wn::ModelOps& ops, int num_params, size_
     throw std::invalid_argument("num_chains must be a multiple of num_weight_sets (chain c reads weight set c / "
                                 "(num_chains / num_weight_sets))");
   plan.weighted = data->weight != nullptr;
-  if (ops.uses_groups) {
+  if (ops.uses_groups && ops.host_params_varying != nullptr) {
+    // varying slopes: Q coefficients vary by group, 0 meaning 1 (the intercept only)
+    const int J = data->num_groups, Q = data->num_varying == 0 ? 1 : data->num_varying;
+    const long long P = static_cast<long long>(num_params) - static_cast<long long>(Q) * (static_cast<long long>(J) + 1);
+    if (Q < 1 || Q > wn::kMaxVaryingCoefficients)
+      throw std::invalid_argument("a model with varying slopes needs 1 <= num_varying <= " +
+                                  std::to_string(wn::kMaxVaryingCoefficients) + ", got " + std::to_string(data->num_varying));
+    if (J < 1 || P < 1)
+      throw std::invalid_argument("a model with varying slopes needs num_params == P + num_varying * (num_groups + 1) with "
+                                  "P >= 1 and num_groups >= 1, got num_params " + std::to_string(num_params) +
+                                  ", num_groups " + std::to_string(J) + ", num_varying " + std::to_string(Q));
+    if (Q - 1 > P)
+      throw std::invalid_argument("the varying slopes belong to the first num_varying - 1 columns of x: num_varying - 1 <= P, "
+                                  "got num_varying " + std::to_string(Q) + ", P " + std::to_string(P));
+    plan.cols = static_cast<int>(P);
+    plan.num_varying = Q;
+  } else if (ops.uses_groups) {
     const int J = data->num_groups;
     if (J < 1 || num_params - J - 1 < 1)
       throw std::invalid_argument("a grouped model needs num_params == P + num_groups + 1 with P >= 1 and num_groups >= 1, "
                                   "got num_params " + std::to_string(num_params) + ", num_groups " + std::to_string(J));
     plan.cols = num_params - J - 1;
+    plan.num_varying = 1;
   }
   if (data->obs_offsets != nullptr) {
     const int G = data->num_datasets;
@@ -299,11 +320,15 @@ void allocate_launch_state(wn_engine& e) {
   HIP_OK(hipMemsetAsync(e.lp_stats.p, 0, 3 * num_chains * sizeof(double), e.stream));
 }
 
-void upload_model_params(wn_engine& e, const wn::ModelOps& ops, const double* model_params) {
+void upload_model_params(wn_engine& e, const wn::ModelOps& ops, const double* model_params, const ObservationPlan& plan) {
   const int num_params = e.D;
   std::vector<double> mp(e.Dp, 1.0);
   if (model_params) std::copy(model_params, model_params + num_params, mp.begin());
-  ops.host_params(mp.data(), num_params);  // the model's own validation / transformation (wn_models.h)
+  // the model's own validation / transformation (wn_models.h); with varying slopes it is told Q
+  if (ops.host_params_varying != nullptr)
+    ops.host_params_varying(mp.data(), num_params, plan.num_varying);
+  else
+    ops.host_params(mp.data(), num_params);
   HIP_OK(hipMemcpyAsync(e.model_params.p, mp.data(), mp.size() * sizeof(double), hipMemcpyHostToDevice, e.stream));
   HIP_OK(hipStreamSynchronize(e.stream));
 }
@@ -345,6 +370,7 @@ void upload_observations(wn_engine& e, const wn::ModelOps& ops, const wn_observa
     HIP_OK(hipMemcpyAsync(e.data_group.p, data->group, N * sizeof(int32_t), hipMemcpyHostToDevice, e.stream));
     e.obs.group = e.data_group.p;
     e.obs.num_groups = data->num_groups;
+    e.obs.num_varying = plan.num_varying;
   }
   if (data->offset != nullptr) {
     e.data_offset.alloc(N);
@@ -401,7 +427,7 @@ void build_engine(wn_engine& e, int model, int num_params, const double* model_p
   allocate_chain_state(e);
   plan_chain_groups(e, cfg, wg_per_cu);  // (before the arena, which has a slice per group)
   allocate_launch_state(e);
-  upload_model_params(e, ops, model_params);
+  upload_model_params(e, ops, model_params, plan);
   upload_observations(e, ops, data, plan);
   e.alloc_monitors();
   wn::prepare_kernels(model, e.geo, e.smem);
@@ -417,6 +443,17 @@ int wn_model_data_columns(int model, int num_params, int num_groups) {
   if (ops == nullptr || !ops->uses_data) return -1;
   if (ops->uses_groups) return num_groups >= 1 ? num_params - num_groups - 1 : -1;
   return ops->scale_param ? num_params - 1 : num_params;
+}
+
+int wn_model_data_columns_varying(int model, int num_params, int num_groups, int num_varying) {
+  if (model < 0 || model >= wn::kMaxModels) return -1;
+  const wn::ModelOps* ops = wn::model_table()[model];
+  if (ops == nullptr || !ops->uses_data) return -1;
+  if (ops->host_params_varying == nullptr) return num_varying > 1 ? -1 : wn_model_data_columns(model, num_params, num_groups);
+  const int Q = num_varying == 0 ? 1 : num_varying;
+  if (Q < 1 || Q > wn::kMaxVaryingCoefficients || num_groups < 1) return -1;
+  const long long P = static_cast<long long>(num_params) - static_cast<long long>(Q) * (static_cast<long long>(num_groups) + 1);
+  return P >= 1 && Q - 1 <= P ? static_cast<int>(P) : -1;
 }
 
 int wn_model_id(const char* name) {

@@ -28,6 +28,8 @@ static_assert(!scale_param<WN_MODEL_TYPE>::value || kUsesData, "kScaleParam need
 static_assert(!uses_row_terms<WN_MODEL_TYPE>::value || kUsesData, "kUsesRowTerms needs kUsesData (wn_model_api.h)");
 static_assert(!(scale_param<WN_MODEL_TYPE>::value && uses_groups<WN_MODEL_TYPE>::value),
               "kScaleParam and kUsesGroups do not combine (wn_model_api.h)");
+static_assert(!varying_slopes<WN_MODEL_TYPE>::value || uses_groups<WN_MODEL_TYPE>::value,
+              "kVaryingSlopes needs kUsesGroups (wn_model_api.h)");
 static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }
 // the pointwise log-likelihood kernels (wn_pointwise.h) exist for data models that declare the hook
 static constexpr bool kPointwise = is_pointwise<WN_MODEL_TYPE>::value;
@@ -333,6 +335,13 @@ template <class M>
 auto call_host_params(double* p, int n, int) -> decltype(M::host_params(p, n), void()) { M::host_params(p, n); }
 template <class M>
 void call_host_params(double*, int, long) {}
+// (a model with varying slopes takes num_varying as a third argument, and is called through this one only)
+template <class M>
+auto call_host_params_varying(double* p, int n, int q, int) -> decltype(M::host_params(p, n, q), void()) {
+  M::host_params(p, n, q);
+}
+template <class M>
+void call_host_params_varying(double*, int, int, long) {}
 template <class M>
 auto call_validate(int n, int) -> decltype(M::validate(n), void()) { M::validate(n); }
 template <class M>
@@ -355,6 +364,9 @@ int WN_CAT(hold_tiles_, WN_MODEL_TAG)(int nw) {
   return 0;
 }
 void WN_CAT(host_params_, WN_MODEL_TAG)(double* p, int n) { call_host_params<WN_MODEL_TYPE>(p, n, 0); }
+void WN_CAT(host_params_varying_, WN_MODEL_TAG)(double* p, int n, int q) {
+  call_host_params_varying<WN_MODEL_TYPE>(p, n, q, 0);
+}
 void WN_CAT(validate_, WN_MODEL_TAG)(int n) { call_validate<WN_MODEL_TYPE>(n, 0); }
 // (a model whose checks depend on whether the engine carries weights takes the flag as a fifth argument)
 template <class M>
@@ -398,7 +410,8 @@ static const ModelOps WN_CAT(kOps_, WN_MODEL_TAG) = {
     uses_row_terms<WN_MODEL_TYPE>::value,
     kPointwise ? &WN_CAT(kPointwiseOps_, WN_MODEL_TAG) : nullptr,
     kPredict ? &WN_CAT(kPredictOps_, WN_MODEL_TAG) : nullptr,
-    kReplicate ? &WN_CAT(kReplicateOps_, WN_MODEL_TAG) : nullptr};
+    kReplicate ? &WN_CAT(kReplicateOps_, WN_MODEL_TAG) : nullptr,
+    varying_slopes<WN_MODEL_TYPE>::value ? &WN_CAT(host_params_varying_, WN_MODEL_TAG) : nullptr};
 static const bool WN_CAT(kRegistered_, WN_MODEL_TAG) = register_model(&WN_CAT(kOps_, WN_MODEL_TAG));
 
 }  // namespace wn

@@ -220,8 +220,12 @@ struct ModelOps {
   const PointwiseOps* pointwise;  // the pointwise log-likelihood (kPointwise); null: the model declares no such hook
   const PredictOps* predict;      // eta, mean and variance of a row (kPredict); null: the model declares no such hook
   const ReplicateOps* replicate;  // simulated replicates of a row (kReplicate); null: the model declares no such hook
+  // a grouped model with varying slopes (kVaryingSlopes; null: the model has no such trait): host_params with
+  // num_varying = Q, which says where the Q scales at the end of the parameter vector begin -- called in its place
+  void (*host_params_varying)(double* params, int num_params, int num_varying);
 };
 constexpr int kMaxModels = 64;
+constexpr int kMaxVaryingCoefficients = 8;  // Q of a model with varying slopes (models/hier_slopes_glm.h: tau_q in lane q)
 inline const ModelOps** model_table() {
   static const ModelOps* table[kMaxModels] = {};
   return table;
@@ -234,7 +238,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 16;
+constexpr int kModelAbiVersion = 17;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

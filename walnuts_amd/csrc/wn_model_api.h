@@ -68,6 +68,13 @@
 //     // Dx = 128 * ceil(P / 128) (host_data's last argument is P).
 //     // wn_engine_create refuses a grouped model without groups and groups for a model without this member.
 //     static constexpr bool kUsesGroups = true;
+//     // ... and, on top of kUsesGroups, VARYING SLOPES: Q = cx.num_varying() >= 1 coefficients vary by group
+//     // (wn_observations::num_varying, 0 meaning 1; at most 8) -- the intercept and the slopes of the FIRST Q - 1
+//     // columns of x -- so theta ends with Q blocks of J effects and Q scales and x has P = num_params - Q (J + 1)
+//     // columns (Q - 1 <= P).  Such a model takes num_varying as host_params' third argument,
+//     // host_params(params, num_params, num_varying), which is called in place of the two-argument form.
+//     // wn_engine_create refuses num_varying > 1 for a model without this member.  models/hier_slopes_glm.h.
+//     static constexpr bool kVaryingSlopes = true;
 //     // ... or, on top of kUsesData and NOT with kUsesGroups (a static_assert), a SCALE PARAMETER as the last
 //     // coordinate: x has P = num_params - 1 columns, stored at the flat stride Dp with column num_params - 1 zero, so
 //     // the row pass never sees the scale (host_data's last argument is P).  models/glm_scale.h.
@@ -140,6 +147,8 @@
 // ... and for grouped data models only (kUsesGroups):
 //   cx.num_groups()                           J, wave-uniform
 //   cx.obs_group(n)                           the group of observation n, in [0, J) (0 <= n < num_obs)
+//   cx.num_varying()                          Q of a model with kVaryingSlopes, wave-uniform (1 for other grouped models)
+//   cx.obs_x(n, col)                          x[n][col], a per-lane load (0 <= n < num_obs, col below the row's stride)
 //   (cx.load_row then fills slot pairs k < Dx / 128 -- columns [128 k, 128 k + 128) -- and zeros the rest without
 //   loading them; a flat model's rows keep the stride Dp and its loads)
 // ... and for data models that declare kUsesRowTerms (eta_n += offset_n; the row's likelihood term and residual times
@@ -159,17 +168,20 @@
 //
 // Registration is a five-line translation unit, wn_kernels_<name>.hip, that the Makefile picks up by its name:
 //   #include "models/my_model.h"
-//   #define WN_MODEL_ID 6                 // 0-5, 15-18 and 24-28 are taken (std_normal, diag_normal, funnel, rw1,
+//   #define WN_MODEL_ID 6                 // 0-5, 15-18, 24-28 and 32-34 are taken (std_normal, diag_normal, funnel, rw1,
 //                                         //   linear_regression, logistic_regression; hier_linear_regression,
 //                                         //   hier_logistic_regression and their _centered forms; poisson_regression,
 //                                         //   neg_binomial_regression, linear_regression_sigma,
-//                                         //   hier_poisson_regression and its _centered form); < 64
+//                                         //   hier_poisson_regression and its _centered form;
+//                                         //   hier_linear_regression_slopes, hier_logistic_regression_slopes,
+//                                         //   hier_poisson_regression_slopes at 32-34); < 64
 //   #define WN_MODEL_TAG my_model         // wn_model_id("my_model") finds it at run time
 //   #define WN_MODEL_TYPE wn::MyModel
 //   #include "wn_kernels.inc"
 // models/rw1.h is a complete example (the reference's AR(1) density with a neighbour-coupled gradient); models/glm.h
 // one of a model conditioned on data (Bayesian linear, logistic and Poisson regression); models/hier_glm.h one with a
-// group channel (hierarchical regression with varying intercepts); models/glm_scale.h one with a scale parameter
+// group channel (hierarchical regression with varying intercepts); models/hier_slopes_glm.h one with varying slopes on
+// top of it (32-34); models/glm_scale.h one with a scale parameter
 // (negative binomial regression, linear regression with an estimated noise level).
 #pragma once
 

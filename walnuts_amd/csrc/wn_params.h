@@ -39,6 +39,9 @@ struct Observations {
   // rows are narrower than theta: stride = 128 * ceil(P / 128) doubles for P = num_params - num_groups - 1 columns
   const int32_t* group;  // [num_obs] (null for other models)
   int32_t num_groups;
+  // ... with varying slopes (kVaryingSlopes): Q >= 1 coefficients vary by group -- the intercept and the first Q - 1
+  // columns of x -- and P = num_params - Q (num_groups + 1); 1 for every other grouped model (0 without groups)
+  int32_t num_varying;
   // per-row offsets (eta_n += offset_n) and weights (the row's likelihood term times weight_n), sliced like y; null:
   // absent.  WEIGHT SETS (chains_per_dataset > 0 with offsets == nullptr): x, y, offset and group are the one shared
   // block of num_obs rows, weight is [sets][num_obs] and chain c reads set c / chains_per_dataset (stride num_obs)

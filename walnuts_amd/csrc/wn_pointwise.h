@@ -91,7 +91,7 @@ struct PointwiseCx {
   const P& Q;
   int tid;
   LaneTables tabs;
-  const double* obs_x;
+  const double* obs_xv;
   const double* obs_yv;
   const int32_t* obs_gv;
   const double* obs_ov;
@@ -101,7 +101,7 @@ struct PointwiseCx {
     tid = opaque_lane_id();
     tabs.load(tid);
     x_stride = uses_groups<Model>::value ? Q.obs.stride : L * EPL;
-    obs_x = Q.obs.x + Q.row0 * x_stride;
+    obs_xv = Q.obs.x + Q.row0 * x_stride;
     obs_yv = Q.obs.y + Q.row0;
     obs_gv = Q.obs.group != nullptr ? Q.obs.group + Q.row0 : nullptr;
     obs_ov = Q.obs.offset != nullptr ? Q.obs.offset + Q.row0 : nullptr;
@@ -119,7 +119,7 @@ struct PointwiseCx {
   // the lane's slots of row n (0 <= n < num_rows, wave-uniform): 16-byte pair loads, as TrajChip::load_row
   __device__ __forceinline__ void load_row(int n, double (&x)[EPL]) const {
     const int nx = x_stride / (2 * L);  // slot pairs the row holds (a grouped model's rows are narrower than theta)
-    const v2f64* row = reinterpret_cast<const v2f64*>(obs_x + static_cast<long long>(n) * x_stride) + tid;
+    const v2f64* row = reinterpret_cast<const v2f64*>(obs_xv + static_cast<long long>(n) * x_stride) + tid;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       if (k < nx) {
@@ -135,6 +135,9 @@ struct PointwiseCx {
   __device__ __forceinline__ double obs_y(int n) const { return obs_yv[n]; }
   __device__ __forceinline__ int num_groups() const { return Q.obs.num_groups; }
   __device__ __forceinline__ int obs_group(int n) const { return obs_gv[n]; }
+  // varying slopes (kVaryingSlopes): Q, and column `col` of row n of x, a per-lane load (as TrajChip::obs_x)
+  __device__ __forceinline__ int num_varying() const { return Q.obs.num_varying; }
+  __device__ __forceinline__ double obs_x(int n, int col) const { return obs_xv[static_cast<long long>(n) * x_stride + col]; }
   __device__ __forceinline__ bool has_offset() const { return obs_ov != nullptr; }
   __device__ __forceinline__ bool has_weight() const { return false; }  // weights are never applied
   __device__ __forceinline__ double obs_offset(int n) const { return obs_ov[n]; }

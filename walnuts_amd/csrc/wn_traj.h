@@ -973,6 +973,12 @@ template <class M, class = void>
 struct uses_groups : std::false_type {};
 template <class M>
 struct uses_groups<M, std::enable_if_t<M::kUsesGroups>> : std::true_type {};
+// ... and a grouped model whose first Q - 1 columns of x carry a slope per group beside the intercept (kVaryingSlopes:
+// cx.num_varying(); theta ends with Q blocks of num_groups effects and Q log scales, models/hier_slopes_glm.h)
+template <class M, class = void>
+struct varying_slopes : std::false_type {};
+template <class M>
+struct varying_slopes<M, std::enable_if_t<M::kVaryingSlopes>> : std::true_type {};
 // ... and a flat data model whose last coordinate is a scale parameter, not a column of x (kScaleParam: x has
 // num_params - 1 columns, stored at the flat stride Dp with column num_params - 1 zero)
 template <class M, class = void>

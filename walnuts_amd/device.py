@@ -142,6 +142,7 @@ def walnuts_device(
     offset=None,
     weights=None,
     weight_sets=None,
+    varying: int = 1,
 ):
     """The device-model sibling of the reference's ``walnuts_pyfunc`` (pyfunc.py:45-286): same keywords, same result
     (a list of per-chain draw arrays carrying ``.warmup``).
@@ -168,6 +169,10 @@ def walnuts_device(
 
     ``data=(x, y, group)``: a grouped model (MODEL_HIER_*), x of
     shape (num_obs, P), groups in [0, J), J = num_params - P - 1; ``datasets=`` then takes triples (x, y, group).
+
+    ``varying=Q`` with ``MODEL_HIER_*_SLOPES`` (1 <= Q <= 8): the intercept and the slopes of the first Q - 1 columns
+    of x vary by group, each with a scale of its own; theta = [beta (P) | u_0 (J) | .. | u_{Q-1} (J) | log tau_0 .. log
+    tau_{Q-1}], ``model_params`` = [prior variances (P) | 1 (Q J) | sigma_0 .. sigma_{Q-1}], J = (num_params - P) / Q - 1.
 
     Count models and an estimated noise level: ``MODEL_POISSON_REGRESSION`` takes data as the linear and logistic
     models; ``MODEL_NEG_BINOMIAL_REGRESSION`` and ``MODEL_LINEAR_REGRESSION_SIGMA`` end theta with the log scale s, so
@@ -226,7 +231,7 @@ def walnuts_device(
         raise ValueError("At least one of num_params or inits must be specified")
     if seed is None:
         seed = int(np.random.randint(0, 2**32 - 1, dtype=np.uint32))
-    obs = observations(lib, model, num_params, data, datasets, offset, weights, weight_sets)
+    obs = observations(lib, model, num_params, data, datasets, offset, weights, weight_sets, varying)
     num_datasets = obs.num_datasets if datasets is not None else 1
     if weight_sets is not None:
         num_datasets = obs.num_weight_sets

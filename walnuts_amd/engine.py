@@ -32,6 +32,14 @@ MODEL_HIER_LINEAR_REGRESSION_CENTERED, MODEL_HIER_LOGISTIC_REGRESSION_CENTERED =
 # hier_poisson_regression(_centered): as MODEL_HIER_*, with Poisson counts.
 MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA = 24, 25, 26
 MODEL_HIER_POISSON_REGRESSION, MODEL_HIER_POISSON_REGRESSION_CENTERED = 27, 28
+# hierarchical regression with varying intercepts and slopes by group, non-centered
+# (walnuts_amd/csrc/models/hier_slopes_glm.h): `varying=Q` coefficients vary by group, the intercept and the slopes of
+# the first Q - 1 columns of x, with independent scales.  theta = [beta (P) | u_0 (J) | .. | u_{Q-1} (J) | log tau_0 ..
+# log tau_{Q-1}], params = [prior variances of beta (P) | 1 (Q J, reserved) | sigma_0 .. sigma_{Q-1}], data = (x, y,
+# group) with P = num_params - Q (J + 1) columns; at varying=1 they are MODEL_HIER_*, bit for bit
+# (ids 29-31 stay free: the tests place run-time models of their own there)
+MODEL_HIER_LINEAR_REGRESSION_SLOPES, MODEL_HIER_LOGISTIC_REGRESSION_SLOPES = 32, 33
+MODEL_HIER_POISSON_REGRESSION_SLOPES = 34
 _dp = _ffi._dp
 
 
@@ -61,11 +69,12 @@ def stream_version(lib_path: Optional[str] = None) -> int:
 class DeviceEngine:
     def __init__(self, model: int, dim: int, num_chains: int, cfg: Optional[_ffi.Config] = None,
                  params: Optional[np.ndarray] = None, lib_path: Optional[str] = None, data=None, datasets=None,
-                 offset=None, weights=None, weight_sets=None):
+                 offset=None, weights=None, weight_sets=None, varying: int = 1):
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
         (num_obs, dim) and y of shape (num_obs,); copied to the device once.  `data=(x, y, group)` for a grouped model
         (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
-        [0, J) with J = dim - P - 1.  A model with a scale parameter
+        [0, J) with J = dim - P - 1.  `varying=Q` (MODEL_HIER_*_SLOPES, 1 <= Q <= 8, Q - 1 <= P): the intercept and
+        the slopes of the first Q - 1 columns of x vary by group, J = (dim - P) / Q - 1.  A model with a scale parameter
         (MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA) takes x of shape (num_obs, dim - 1): its last
         coordinate is s, not a column of x.  The count models (MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION,
         MODEL_HIER_POISSON_REGRESSION*) need every y to be a finite non-negative integer.
@@ -98,7 +107,7 @@ class DeviceEngine:
             raise ValueError("model params must have num_params entries")
         h, err = C.c_void_p(), C.c_void_p()
         pp = None if p is None else p.ctypes.data_as(_dp)
-        obs = observations(self.lib, model, self.D, data, datasets, offset, weights, weight_sets)
+        obs = observations(self.lib, model, self.D, data, datasets, offset, weights, weight_sets, varying)
         # (one weight set is one weight vector: such an engine holds no datasets)
         self._several = datasets is not None or (obs is not None and obs.num_weight_sets > 1)
         # rows per dataset (the pointwise entry points size their outputs with them)

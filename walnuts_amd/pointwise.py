@@ -55,7 +55,7 @@ def _ones(num_params: int) -> np.ndarray:
 
 
 def log_predictive(model: int, chains, *, num_params: int, data=None, datasets=None, offset=None, weight_sets=None,
-                   held_out=None, cfg=None, lib_path: Optional[str] = None) -> PointwisePredictive:
+                   held_out=None, cfg=None, lib_path: Optional[str] = None, varying: int = 1) -> PointwisePredictive:
     """Score draws on rows: lpd, mean, var and count per row (PointwisePredictive).
 
     `chains`: one MarkovChains of G * k chains -- block g is scored on dataset g (`datasets=`), or on the shared rows as
@@ -63,7 +63,8 @@ def log_predictive(model: int, chains, *, num_params: int, data=None, datasets=N
     of ``chain_blocks``).  The rows are given as for DeviceEngine (`data=`, `datasets=`, `offset=`); weights are never
     applied, `weight_sets=` (W, N) only says which block meets which rows.  `held_out`: a mask shaped like the output
     ([total rows]; [W, N] with weight sets) of the rows to evaluate; default every row, with `weight_sets=` the rows of
-    weight 0 (`weight_sets == 0`: each fold scored on what it did not see).  Model parameters are not needed."""
+    weight 0 (`weight_sets == 0`: each fold scored on what it did not see).  `varying` as for DeviceEngine.  Model
+    parameters are not needed."""
     if isinstance(chains, MarkovChains):
         blocks = None
     else:
@@ -78,7 +79,7 @@ def log_predictive(model: int, chains, *, num_params: int, data=None, datasets=N
             held_out = ws == 0
     G = ws.shape[0] if weight_sets is not None else (len(list(datasets)) if datasets is not None else 1)
     mask = None if held_out is None else np.asarray(held_out) != 0
-    common = dict(cfg=cfg, params=_ones(num_params), lib_path=lib_path)
+    common = dict(cfg=cfg, params=_ones(num_params), lib_path=lib_path, varying=varying)
     if blocks is None:
         e = DeviceEngine(model, num_params, G, data=data, datasets=datasets, offset=offset,
                          weight_sets=None if weight_sets is None or G == 1 else np.ones_like(ws), **common)
@@ -123,7 +124,7 @@ def log_predictive(model: int, chains, *, num_params: int, data=None, datasets=N
 
 
 def kfold_elpd(model: int, views, *, num_params: int, data, weight_sets, offset=None, cfg=None,
-               lib_path: Optional[str] = None) -> PointwisePredictive:
+               lib_path: Optional[str] = None, varying: int = 1) -> PointwisePredictive:
     """K-fold cross-validation from the K refits of ``walnuts_device(..., weight_sets=weight_sets)``: `views` are the
     fits' draws (one MarkovChains of K * k chains, or the K views of ``chain_blocks``), and every row takes its lpd,
     mean, var and count from the ONE set that held it out (weight 0).  -> PointwisePredictive with [N] arrays; `.elpd`
@@ -138,7 +139,7 @@ def kfold_elpd(model: int, views, *, num_params: int, data, weight_sets, offset=
         bad = int(np.flatnonzero(times != 1)[0])
         raise ValueError(f"every row must be held out by exactly one weight set: row {bad} is held out by {int(times[bad])}")
     res = log_predictive(model, views, num_params=num_params, data=data, offset=offset, weight_sets=ws, held_out=held,
-                         cfg=cfg, lib_path=lib_path)
+                         cfg=cfg, lib_path=lib_path, varying=varying)
     fold = np.argmax(held, axis=0)
     cols = np.arange(ws.shape[1])
     return PointwisePredictive(res.lpd[fold, cols], res.mean[fold, cols], res.var[fold, cols], res.count[fold, cols])

@@ -73,7 +73,7 @@ def _as_blocks(chains):
 
 
 def predict(model: int, chains, *, num_params: int, data=None, datasets=None, offset=None, weight_sets=None, rows=None,
-            cfg=None, lib_path: Optional[str] = None) -> Prediction:
+            cfg=None, lib_path: Optional[str] = None, varying: int = 1) -> Prediction:
     """Predict rows from draws: per row the moments of the linear predictor and of the expected response, and the mean
     noise variance (Prediction; `.var` / `.sd` are the predictive variance and standard deviation of a new observation).
 
@@ -81,8 +81,8 @@ def predict(model: int, chains, *, num_params: int, data=None, datasets=None, of
     `chains`: one MarkovChains of G * k chains -- block g predicts dataset g (`datasets=`), or the shared rows as weight
     set g (`weight_sets=`, which only says how many blocks meet the rows: weights are never applied), or all chains
     `data=` -- or a sequence of G MarkovChains, one per block (the views of ``chain_blocks``).  `rows`: a mask shaped like
-    the output ([total rows]; [W, N] with weight sets) of the rows to evaluate, default every row.  Model parameters are
-    not needed."""
+    the output ([total rows]; [W, N] with weight sets) of the rows to evaluate, default every row.  `varying` as for
+    DeviceEngine.  Model parameters are not needed."""
     lib = _ffi.load_library(lib_path)
     blocks = _as_blocks(chains)
     if data is not None:
@@ -96,7 +96,7 @@ def predict(model: int, chains, *, num_params: int, data=None, datasets=None, of
             raise ValueError(f"weight_sets must have shape (W, num_obs), got {ws.shape}")
     G = ws.shape[0] if ws is not None else (len(datasets) if datasets is not None else 1)
     mask = None if rows is None else np.asarray(rows) != 0
-    common = dict(cfg=cfg, params=_ones(num_params), lib_path=lib_path)
+    common = dict(cfg=cfg, params=_ones(num_params), lib_path=lib_path, varying=varying)
     if blocks is None:
         e = DeviceEngine(model, num_params, G, data=data, datasets=datasets, offset=offset,
                          weight_sets=None if ws is None or G == 1 else np.ones_like(ws), **common)
@@ -139,7 +139,8 @@ def predict(model: int, chains, *, num_params: int, data=None, datasets=None, of
 
 
 def predict_draws(model: int, chains, *, num_params: int, data=None, datasets=None, offset=None, weight_sets=None,
-                  what: str = "mean", block: int = 0, cfg=None, lib_path: Optional[str] = None) -> MarkovChains:
+                  what: str = "mean", block: int = 0, cfg=None, lib_path: Optional[str] = None,
+                  varying: int = 1) -> MarkovChains:
     """The predictions per draw as MarkovChains on the device: k chains with the source chains' lengths and one dimension
     per row, holding E[y | theta, x_n] (`what="mean"`) or the linear predictor (`what="eta"`) -- `.quantiles([0.05, 0.5,
     0.95])` is a credible band of the prediction, `.r_hat()`, `.effective_sample_size()` and
@@ -155,7 +156,8 @@ def predict_draws(model: int, chains, *, num_params: int, data=None, datasets=No
     ws = None if weight_sets is None else np.asarray(weight_sets, dtype=np.float64)
     G = ws.shape[0] if ws is not None else (len(datasets) if datasets is not None else 1)
     e = DeviceEngine(model, num_params, G, cfg=cfg, params=_ones(num_params), lib_path=lib_path, data=data,
-                     datasets=datasets, offset=offset, weight_sets=None if ws is None or G == 1 else np.ones_like(ws))
+                     datasets=datasets, offset=offset, weight_sets=None if ws is None or G == 1 else np.ones_like(ws),
+                     varying=varying)
     try:
         return e.predict_chains(chains, block=block, what=what)
     finally:

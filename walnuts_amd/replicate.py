@@ -41,18 +41,20 @@ def _derived(stats, n):
     return mean, var
 
 
-def _engine(lib, model, num_params, data, datasets, offset, weight_sets, cfg, lib_path):
+def _engine(lib, model, num_params, data, datasets, offset, weight_sets, cfg, lib_path, varying=1):
     ws = None if weight_sets is None else np.asarray(weight_sets, dtype=np.float64)
     if ws is not None and ws.ndim != 2:
         raise ValueError(f"weight_sets must have shape (W, num_obs), got {ws.shape}")
     G = ws.shape[0] if ws is not None else (len(datasets) if datasets is not None else 1)
     e = DeviceEngine(model, num_params, G, cfg=cfg, params=_ones(num_params), lib_path=lib_path, data=data,
-                     datasets=datasets, offset=offset, weight_sets=None if ws is None or G == 1 else np.ones_like(ws))
+                     datasets=datasets, offset=offset, weight_sets=None if ws is None or G == 1 else np.ones_like(ws),
+                     varying=varying)
     return e, G, ws
 
 
 def replicate_draws(model: int, chains, *, num_params: int, seed: int, data=None, datasets=None, offset=None,
-                    weight_sets=None, block: int = 0, cfg=None, lib_path: Optional[str] = None) -> MarkovChains:
+                    weight_sets=None, block: int = 0, cfg=None, lib_path: Optional[str] = None,
+                    varying: int = 1) -> MarkovChains:
     """y_rep per draw and row as MarkovChains on the device: k chains with the source chains' lengths and one dimension
     per row.  `data`, `datasets`, `offset`, `weight_sets`, `block` as for ``predict_draws`` (y is never read); a replicate
     depends on (seed, chain, draw, row) alone."""
@@ -63,7 +65,7 @@ def replicate_draws(model: int, chains, *, num_params: int, seed: int, data=None
         data = _rows_of(lib, model, num_params, data)
     if datasets is not None:
         datasets = [_rows_of(lib, model, num_params, d) for d in datasets]
-    e, _, _ = _engine(lib, model, num_params, data, datasets, offset, weight_sets, cfg, lib_path)
+    e, _, _ = _engine(lib, model, num_params, data, datasets, offset, weight_sets, cfg, lib_path, varying)
     try:
         return e.replicate_chains(chains, seed, block=block)
     finally:
@@ -71,14 +73,15 @@ def replicate_draws(model: int, chains, *, num_params: int, seed: int, data=None
 
 
 def posterior_predictive_check(model: int, chains, *, num_params: int, seed: int, data=None, datasets=None, offset=None,
-                               weight_sets=None, rows=None, cfg=None, lib_path: Optional[str] = None) -> PredictiveCheck:
+                               weight_sets=None, rows=None, cfg=None, lib_path: Optional[str] = None,
+                               varying: int = 1) -> PredictiveCheck:
     """Posterior predictive checks of a fit: `data=(x, y[, group])` (or `datasets=`) are the observations the check
     compares with, `chains` one MarkovChains of G * k chains (block g meets dataset / weight set g), `rows` a mask shaped
     as for ``predict`` of the rows that enter the statistics (default: all).  Weights are never applied."""
     lib = _ffi.load_library(lib_path)
     if not isinstance(chains, MarkovChains):
         raise ValueError("chains must be a MarkovChains")
-    e, G, ws = _engine(lib, model, num_params, data, datasets, offset, weight_sets, cfg, lib_path)
+    e, G, ws = _engine(lib, model, num_params, data, datasets, offset, weight_sets, cfg, lib_path, varying)
     try:
         mask = None if rows is None else np.asarray(rows) != 0
         if mask is not None and G == 1 and ws is not None:
