@@ -3,8 +3,8 @@ hierarchical Poisson regression (models/glm.h, models/glm_scale.h, models/hier_g
 
   * the count maths (wnd::dlog1p, dsoftplus, dlgamma_diff, ddigamma_diff) on the device equal the host build of the same
     source bit for bit on 2^20 arguments each (wn_internal_count_math_probe);
-  * device = emulation, bit for bit, for the five models at (1, 2), (1, 4) and (1, 16), over logp_grad, warmup and
-    sampling transitions; (1, 8) for determinism and against NumPy;
+  * device = emulation, bit for bit, for the five models at (1, 2), (1, 4), (1, 8) and (1, 16), over logp_grad, warmup
+    and sampling transitions; (1, 8) also for determinism and against NumPy;
   * posterior means and variances within 5 Monte Carlo standard errors of quadrature (Poisson intercept + slope and
     negative binomial intercept + s on 2-D grids; linear_regression_sigma with beta integrated out, 1-D over s), and
     R-hat < 1.01;
@@ -86,9 +86,11 @@ def run(lib, model, D, C, data, mp, geometry, fma, warm=6, samp=6):
     return out
 
 
+# (D = 512 at eight per lane: every slot filled, the scale parameter of glm_scale.h and tau in the last slot of lane 63)
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("model", ALL, ids=ALL_IDS)
-@pytest.mark.parametrize("D,N,geometry", [(5, 70, (1, 2)), (130, 9, (1, 4)), (1000, 61, (1, 16)), (3, 3, (1, 16))])
+@pytest.mark.parametrize("D,N,geometry", [(5, 70, (1, 2)), (130, 9, (1, 4)), (1000, 61, (1, 16)), (3, 3, (1, 16)),
+                                          (300, 9, (1, 8)), (512, 5, (1, 8))])
 @pytest.mark.parametrize("fma", [0, 1])
 def test_device_equals_emulation(gpu, model, D, N, geometry, fma):
     sim = simbuild.build()

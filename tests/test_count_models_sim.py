@@ -27,7 +27,7 @@ POIS, NB, LSIG = wa.MODEL_POISSON_REGRESSION, wa.MODEL_NEG_BINOMIAL_REGRESSION, 
 HPOIS, HPOIS_C = wa.MODEL_HIER_POISSON_REGRESSION, wa.MODEL_HIER_POISSON_REGRESSION_CENTERED
 FLAT = (POIS, NB, LSIG)
 FLAT_IDS = ["poisson", "negbin", "linear_sigma"]
-SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 16))
+SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
 CSRC = os.path.join(os.path.dirname(HERE), "walnuts_amd", "csrc")
 
 

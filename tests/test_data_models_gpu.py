@@ -1,7 +1,7 @@
 """GPU tier: models conditioned on data (walnuts_amd/csrc/models/glm.h) on the MI355X.
 
   * device = emulation, bit for bit: the same kernel source under tests/cpusim and on gfx950, same geometry asked of both;
-  * (1, 8) -- eight elements per lane, a geometry the emulation does not build -- against NumPy and for determinism;
+  * (1, 8) -- eight elements per lane, the default for 257-512 parameters -- also against NumPy and for determinism;
   * the linear model against its closed-form posterior, the logistic model against its Laplace approximation;
   * the drop-in call with data, draws on the host and kept on the device;
   * the GLM edge matrix of test_data_models_sim.py (N around the block size, D at the padding boundary, saturated
@@ -47,7 +47,8 @@ def run(lib, model, D, C, data, s2, geometry, fma, warm=6, samp=6):
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("model", [LIN, LOG])
 @pytest.mark.parametrize("D,N,geometry", [(5, 70, (1, 2)), (150, 130, (1, 4)), (1000, 60, (1, 16)),
-                                          (1000, 7, (1, 16)), (150, 5, (1, 4))])  # (odd N at B = 2; N < B = 8)
+                                          (1000, 7, (1, 16)), (150, 5, (1, 4)),  # (odd N at B = 2; N < B = 8)
+                                          (300, 9, (1, 8)), (512, 5, (1, 8))])  # (N = 2 B + 1 and B + 1 at B = 4; no padding)
 @pytest.mark.parametrize("fma", [0, 1])
 def test_device_equals_emulation(gpu, model, D, N, geometry, fma):
     sim = simbuild.build()

@@ -20,7 +20,7 @@ import walnuts_amd as wa  # noqa: E402
 from walnuts_amd import models  # noqa: E402
 
 LIN, LOG = wa.MODEL_LINEAR_REGRESSION, wa.MODEL_LOGISTIC_REGRESSION
-# one wavefront per chain at 2, 4 and 16 elements per lane (the emulation's one-wavefront geometries), with padding
+# one wavefront per chain at 2, 4 and 16 elements per lane, with padding
 DIMS = (5, 150, 1000)
 
 
@@ -248,7 +248,7 @@ def test_runtime_compiled_copy_of_the_glm_header(sim, tmp_path):
 # Rows are taken in register blocks of B = 16 / 8 / 4 / 2 rows at 2 / 4 / 8 / 16 elements per lane (models/glm.h): the
 # matrix puts N at 1, B - 1, B, B + 1 (and an odd N at B = 2: the last block holds one of its two rows) and D at 1 and
 # at the padding boundary 64 * EPL - 1, 64 * EPL (the one-wavefront kernels take nothing larger).
-SIM_GLM_GEOMETRIES = ((1, 2), (1, 4), (1, 16))
+SIM_GLM_GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
 GLM_KINDS = {LIN: ("plain", "big_y"), LOG: ("mixed", "y0", "y1")}
 
 

@@ -1,7 +1,7 @@
 """GPU tier: many datasets of one data model in one engine, on the MI355X.
 
-  * device = emulation, bit for bit, for batched engines at (1, 2), (1, 4) and (1, 16), both arithmetic modes;
-  * (1, 8), which the emulation does not build: batched = standalone engines on the device, bit for bit;
+  * device = emulation, bit for bit, for batched engines at (1, 2), (1, 4), (1, 8) and (1, 16), both arithmetic modes;
+  * (1, 8) with four datasets: batched = standalone engines on the device, bit for bit;
   * the per-dataset statistics = standalone device engines' pooled ones, bit for bit, at 300 chains per dataset (each
     dataset's 256-chain runs start at its own offset);
   * an observation block over 4 GiB after padding (a 32-bit byte offset would wrap): gradients of the last datasets'
@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.timeout(3600)
 @pytest.mark.parametrize("model", [LIN, LOG])
-@pytest.mark.parametrize("geometry", [(1, 2), (1, 4), (1, 16)])
+@pytest.mark.parametrize("geometry", [(1, 2), (1, 4), (1, 8), (1, 16)])
 @pytest.mark.parametrize("fma", [0, 1])
 def test_device_equals_emulation(gpu, model, geometry, fma):
     sim = simbuild.build()

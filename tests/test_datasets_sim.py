@@ -21,8 +21,8 @@ import walnuts_amd as wa  # noqa: E402
 from walnuts_amd import models  # noqa: E402
 from test_data_models_sim import LIN, LOG, make_data  # noqa: E402
 
-SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 16))
-DIM = {2: 7, 4: 150, 16: 300}  # one wavefront per chain, with padding
+SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
+DIM = {2: 7, 4: 150, 8: 300, 16: 300}  # one wavefront per chain, with padding
 
 
 @pytest.fixture(scope="module")

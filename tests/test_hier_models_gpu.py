@@ -1,8 +1,7 @@
 """GPU tier: hierarchical regression with varying intercepts by group (walnuts_amd/csrc/models/hier_glm.h) on the MI355X.
 
-  * device = emulation, bit for bit, for all four models at (1, 2), (1, 4) and (1, 16), both arithmetic modes, over
-    logp_grad, warmup and sampling transitions; (1, 8), which the emulation does not build, against NumPy and for
-    determinism;
+  * device = emulation, bit for bit, for all four models at (1, 2), (1, 4), (1, 8) and (1, 16), both arithmetic modes,
+    over logp_grad, warmup and sampling transitions; (1, 8) also against NumPy and for determinism;
   * hierarchical linear regression against its exact posterior: given s = log tau, (beta, a) is Gaussian and
     p(s | y) is closed-form up to a constant, so a quadrature over s gives the exact posterior means and variances of
     beta, tau and the group effects; both parameterizations' draws of 4 096 chains within MCSE-based bounds;
@@ -49,7 +48,11 @@ def run(lib, model, D, C, data, mp, geometry, fma, warm=6, samp=6):
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("model", HIER, ids=IDS)
 @pytest.mark.parametrize("P,J,N,geometry", [(3, 6, 70, (1, 2)), (130, 20, 9, (1, 4)), (129, 500, 61, (1, 16)),
-                                            (1, 1, 3, (1, 16))])
+                                            (1, 1, 3, (1, 16)),
+                                            # eight per lane, rows narrower than theta: nx = 2 of 4 slot pairs; nx = 1,
+                                            # effects over three pairs, tau at coordinate 256 (first slot of a pair);
+                                            # nx = 3, D = 512, tau in the very last slot
+                                            (200, 150, 50, (1, 8)), (100, 156, 13, (1, 8)), (300, 211, 13, (1, 8))])
 @pytest.mark.parametrize("fma", [0, 1])
 def test_device_equals_emulation(gpu, model, P, J, N, geometry, fma):
     sim = simbuild.build()

@@ -25,7 +25,7 @@ HLIN, HLOG = wa.MODEL_HIER_LINEAR_REGRESSION, wa.MODEL_HIER_LOGISTIC_REGRESSION
 HLIN_C, HLOG_C = wa.MODEL_HIER_LINEAR_REGRESSION_CENTERED, wa.MODEL_HIER_LOGISTIC_REGRESSION_CENTERED
 HIER = (HLIN, HLOG, HLIN_C, HLOG_C)
 IDS = ["linear", "logistic", "linear_c", "logistic_c"]
-SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 16))
+SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
 
 
 def is_logistic(model):
@@ -162,12 +162,14 @@ def test_logp_grad_matches_numpy_and_finite_differences(sim, model, P, J, N, fma
 
 
 # ---- the edge matrix against the long-double reference --------------------------------------------------------------
-# Rows go in blocks of B = 16 / 8 / 2 at 2 / 4 / 16 elements per lane (the emulation's one-wavefront geometries): N at
+# Rows go in blocks of B = 16 / 8 / 4 / 2 at 2 / 4 / 8 / 16 elements per lane (the one-wavefront geometries): N at
 # 1, B - 1, B, B + 1.  (P, J) put P at 1, 127, 128, 129 (the narrow row stride Dx = 128 ceil(P / 128)), J at 1 and
-# large (empty groups), and num_params at the padding boundaries Dp = 64 EPL and Dp +- 1 up to 1 024.
+# large (empty groups), and num_params at the padding boundaries Dp = 64 EPL and Dp +- 1 up to 1 024.  Eight per lane:
+# rows of 1, 2 and 3 slot pairs out of theta's 4, tau at coordinate 256 (the first slot of a pair) and in the last slot.
 EDGE_SHAPES = {
     2: [(1, 1), (1, 126), (60, 67), (100, 20)],                  # D = 3, 128, 128, 121
     4: [(127, 1), (128, 1), (129, 126), (1, 254), (127, 128)],   # D = 129, 130, 256, 256, 256
+    8: [(100, 156), (200, 150), (129, 382), (300, 211), (257, 1)],  # D = 257, 351, 512, 512, 259
     16: [(129, 894), (128, 500), (1000, 23), (300, 212)],         # D = 1024, 629, 1024, 513
 }
 
@@ -285,7 +287,7 @@ def test_datasets_equal_standalone_engines(sim, model, geometry, fma):
     g k, bit for bit: positions, logp, depths, grad-evals, rng draws, step sizes, Adam state and estimator planes over
     single and fused warmup launches and sampling."""
     epl = geometry[1]
-    P, J = {2: (3, 6), 4: (130, 7), 16: (200, 40)}[epl]
+    P, J = {2: (3, 6), 4: (130, 7), 8: (200, 150), 16: (200, 40)}[epl]
     B = hp.block_rows(epl)
     k = 2
     datasets, mp = make_grouped_datasets(model, P, J, [1, B + 1, 2 * B + 3], seed=40 + epl)

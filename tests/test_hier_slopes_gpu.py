@@ -5,7 +5,7 @@ hier_slopes_glm.h) on the MI355X.
     modes, with and without offsets and weights: logp_grad, warmup and sampling transitions, and the outputs of the
     pointwise, predict and replicate hooks;
   * one varying coefficient (varying=1) = MODEL_HIER_*, bit for bit, at every one-wavefront geometry;
-  * (1, 8), which the emulation does not build, against NumPy and for determinism;
+  * (1, 8) also against NumPy and for determinism;
   * the drop-in call with data=(x, y, group), varying=2 and with datasets=, draws on the host and kept on the device;
   * linear, Q = 2, against its exact posterior: given (s_0, s_1), (beta, tau_q u_q) is Gaussian and p(s | y) is
     closed-form up to a constant, so a two-dimensional quadrature gives the exact means and variances."""

@@ -36,13 +36,13 @@ SIBLING = {SLIN: wa.MODEL_HIER_LINEAR_REGRESSION, SLOG: wa.MODEL_HIER_LOGISTIC_R
            SPOIS: wa.MODEL_HIER_POISSON_REGRESSION}
 FLAT = {SLIN: wa.MODEL_LINEAR_REGRESSION, SLOG: wa.MODEL_LOGISTIC_REGRESSION, SPOIS: wa.MODEL_POISSON_REGRESSION}
 KIND = {SLIN: hr.NORMAL, SLOG: hr.BERNOULLI, SPOIS: hr.POISSON}
-SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 16))
+SIM_GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
 # (P, J, Q, N, geometry): the only column varies, one group, N odd and below a block; empty groups, N no multiple of
 # B = 16 nor of 64; u blocks across the 128-coordinate slot-pair boundary at Dx = 256; D = 882; Q at its cap with every
-# column varying
+# column varying; eight per lane with rows of 2 slot pairs out of 4 and N = 5 B + 1
 SHAPES = [(1, 1, 2, 3, (1, 16)), (3, 6, 2, 70, (1, 2)), (130, 20, 3, 9, (1, 4)), (129, 250, 3, 61, (1, 16)),
-          (7, 2, 8, 20, (1, 4))]
-SHAPE_IDS = ["P1J1Q2", "P3J6Q2", "P130J20Q3", "P129J250Q3", "P7J2Q8"]
+          (7, 2, 8, 20, (1, 4)), (130, 60, 3, 21, (1, 8))]
+SHAPE_IDS = ["P1J1Q2", "P3J6Q2", "P130J20Q3", "P129J250Q3", "P7J2Q8", "P130J60Q3_epl8"]
 SEED = 2 ** 33 + 5
 
 
@@ -309,7 +309,7 @@ def test_finite_differences_of_every_coordinate_class(sim, model):
 def test_one_varying_coefficient_is_the_hier_model_bit_for_bit(sim, model, geometry, fma):
     """varying=1: logp_grad and a warmup + sampling drive give the bits of MODEL_HIER_*, with and without row terms."""
     epl = geometry[1]
-    P, J = {2: (3, 6), 4: (130, 7), 16: (200, 40)}[epl]
+    P, J = {2: (3, 6), 4: (130, 7), 8: (200, 150), 16: (200, 40)}[epl]
     N = 2 * hp.block_rows(epl) + 3
     for terms in (False, True):
         c = make_slopes(model, P, J, 1, N, seed=40 + epl, terms=terms)
@@ -368,7 +368,7 @@ def row_const(model, y):
 
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("model", SLOPES, ids=IDS)
-@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2], SHAPES[4]], ids=[SHAPE_IDS[1], SHAPE_IDS[2], SHAPE_IDS[4]])
+@pytest.mark.parametrize("shape", [SHAPES[i] for i in (1, 2, 4, 5)], ids=[SHAPE_IDS[i] for i in (1, 2, 4, 5)])
 def test_hooks(sim, model, shape):
     """pointwise(): every row term against long double, and sum_n w_n (l_n - c_n) + prior against logp_grad's logp.
     predict(): eta is pointwise()'s through an exactly vanishing residual (linear: y := eta gives l_n = c_n, bit for

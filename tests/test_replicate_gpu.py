@@ -56,12 +56,22 @@ def test_invariance_under_grid_mask_and_row_order(gpu, monkeypatch):
     check_invariance(None, monkeypatch)
 
 
+@pytest.mark.parametrize("geometry", GEOMETRIES[1:])
+def test_invariance_at_the_wider_geometries(gpu, monkeypatch, geometry):
+    check_invariance(None, monkeypatch, geometry)
+
+
 def test_seeds_ids_and_the_engines_own_streams(gpu):
     check_seeds_and_streams(None)
 
 
 def test_nan_rule_one_live_row_and_an_all_masked_block(gpu):
     check_nan_rule_and_masks(None)
+
+
+@pytest.mark.parametrize("geometry", GEOMETRIES[1:])
+def test_nan_rule_and_masks_at_the_wider_geometries(gpu, geometry):
+    check_nan_rule_and_masks(None, geometry)
 
 
 def test_wrappers(gpu):

@@ -149,25 +149,35 @@ def test_small_blocks(sim, model, N):
     check_reduction(f)
 
 
-def check_invariance(lib, monkeypatch):
+@pytest.mark.timeout(3600)
+@pytest.mark.parametrize("model", MODELS, ids=IDS)
+@pytest.mark.parametrize("geometry", [(1, 4), (1, 8)])
+@pytest.mark.parametrize("N", [1, 63])
+def test_small_blocks_at_four_and_eight_per_lane(sim, model, geometry, N):
+    f = rep_case(sim, model, geometry, 1, N=N)
+    check_purity(sim, f)
+    check_reduction(f)
+
+
+def check_invariance(lib, monkeypatch, geometry=(1, 2)):
     """one workgroup instead of one per item: identical bits everywhere, with and without the mask.  Another row order:
     row j of the permuted block is drawn on stream j from ITS mu, so the permuted block's replicate is the probe fed the
     permuted mu -- nothing but the key and the row's own mu and scale enters."""
     for model in (NB, HLOG):
-        base = bits(rep_case(lib, model, (1, 2), 1))
+        base = bits(rep_case(lib, model, geometry, 1))
         monkeypatch.setenv("WALNUTS_AMD_POINTWISE_GRID", "1")
-        other = bits(rep_case(lib, model, (1, 2), 1))
+        other = bits(rep_case(lib, model, geometry, 1))
         monkeypatch.delenv("WALNUTS_AMD_POINTWISE_GRID")
         assert len(base) == len(other) and all(hm.same_bits(a, b) for a, b in zip(base, other)), model
     model, N = NB, 65
-    c = rep_case_data(model, 2, N, seed=5)
+    c = rep_case_data(model, geometry[1], N, seed=5)
     theta = thetas_for(model, c["D"], 2, seed=1)
     perm = np.random.default_rng(3).permutation(N)
-    e = engine(lib, model, c, 1, (1, 2), 1, offset=c["offset"])
+    e = engine(lib, model, c, 1, geometry, 1, offset=c["offset"])
     mu = e.predict(theta)[1]
     e.close()
     pc = dict(c, data=tuple(a[perm] for a in c["data"]), offset=c["offset"][perm])
-    e = engine(lib, model, pc, 1, (1, 2), 1, offset=pc["offset"])
+    e = engine(lib, model, pc, 1, geometry, 1, offset=pc["offset"])
     mu_p, rep_p = e.predict(theta)[1], e.replicate(theta, SEED)
     e.close()
     assert hm.same_bits(mu_p, mu[:, perm])
@@ -178,6 +188,11 @@ def check_invariance(lib, monkeypatch):
 
 def test_invariance_under_grid_mask_and_row_order(sim, monkeypatch):
     check_invariance(sim, monkeypatch)
+
+
+@pytest.mark.parametrize("geometry", GEOMETRIES[1:])
+def test_invariance_at_the_wider_geometries(sim, monkeypatch, geometry):
+    check_invariance(sim, monkeypatch, geometry)
 
 
 def check_seeds_and_streams(lib):
@@ -220,14 +235,14 @@ def test_seeds_ids_and_the_engines_own_streams(sim):
     check_seeds_and_streams(sim)
 
 
-def check_nan_rule_and_masks(lib):
+def check_nan_rule_and_masks(lib, geometry=(1, 2)):
     """a draw whose Poisson link overflows on a live row has NaN in all six replicate statistics and only there; one live
     row; a block that is masked out entirely: sums 0, min +inf, max -inf"""
     model, N = POIS, 65
-    c = case_for(model, SMALL[2], N, seed=21)
+    c = case_for(model, SMALL[geometry[1]], N, seed=21)
     theta = overflowing_theta(model, c, thetas_for(model, c["D"], 3, seed=4))   # the last position overflows row 0
     ch = wa.MarkovChains.from_host([theta], lib_path=lib)
-    e = engine(lib, model, c, 1, (1, 2), 1, offset=c["offset"])
+    e = engine(lib, model, c, 1, geometry, 1, offset=c["offset"])
     mu = e.predict(theta)[1]
     assert mu[2, 0] == np.inf and np.isfinite(mu[:2]).all()
     rep, obs = e.replicate_check(ch, SEED)
@@ -242,8 +257,10 @@ def check_nan_rule_and_masks(lib):
     one = np.arange(N) == 7
     rep1, obs1 = e.replicate_check(ch, SEED, one)
     y = c["data"][1]
+    block = download(e.replicate_chains(ch, SEED), 3, (3,))[0]   # the check's draw i of chain 0 is keyed (chain 0, draw i):
+    assert hm.same_bits(block[0], full[0])                       # the block's row i, and replicate()'s position 0 only
     for i in range(2):
-        q = full[i, 7]
+        q = block[i, 7]
         assert rep1[0, 0, i] == q and rep1[1, 0, i] == q * q and rep1[2, 0, i] == q and rep1[3, 0, i] == q
         assert rep1[4, 0, i] == float(q == 0)
         assert obs1[0, 0, i] == y[7] and obs1[2, 0, i] == y[7] and obs1[3, 0, i] == y[7]
@@ -255,6 +272,11 @@ def check_nan_rule_and_masks(lib):
 
 def test_nan_rule_one_live_row_and_an_all_masked_block(sim):
     check_nan_rule_and_masks(sim)
+
+
+@pytest.mark.parametrize("geometry", GEOMETRIES[1:])
+def test_nan_rule_and_masks_at_the_wider_geometries(sim, geometry):
+    check_nan_rule_and_masks(sim, geometry)
 
 
 def check_generated_quantiles(f):

@@ -159,8 +159,8 @@ def run(lib, model, D, C, geometry, *, tpl, seed=1234, step=None, warmup=2, fma=
 
 
 # ---- the launch boundary: 9 x 1, 4 x 2 + 1, 3 x 3, 8 + 1 --------------------------------------------------------------
-# (first column: the tier that has the geometry -- the emulation is built with a cross-section of them, (1, 16) and
-# (2, 8) among them -- or None for both)
+# (first column: the tier that runs the row -- the emulation is built with a cross-section of the geometries, (1, 8),
+# (1, 16) and (2, 8) among them -- or None for both)
 GEOMETRIES = tiered([
     (None, "std_normal", 1024, (1, 16), 1),    # the headline kernel: the other end parked in accumulator registers
     (None, "std_normal", 1024, (1, 16), 0),
@@ -171,6 +171,7 @@ GEOMETRIES = tiered([
     (None, "diag_normal", 1024, (2, 8), 1),    # ... with 8 elements per lane
     (None, "std_normal", 1000, (1, 16), 1),    # padding lanes: their momentum is zero
     (None, "diag_normal", 1000, (1, 16), 0),
+    ("sim", "std_normal", 512, (1, 8), 1),     # (the emulated half of the (1, 8) row above)
 ])
 
 

@@ -2,7 +2,7 @@
 MI355X.
 
   * device = emulation, bit for bit, with offsets and weights (a zero-weight row inside a block) at N = B - 1 and B + 1,
-    (1, 2) and (1, 16), both arithmetic modes: logistic, negative binomial and hierarchical logistic regression;
+    the four one-wavefront geometries, both arithmetic modes: logistic, negative binomial and hierarchical logistic regression;
   * weight sets (W = 4, k = 4): each set's block equals the emulation's;
   * the edge matrix of test_weights_sim.py against the high-precision reference, Poisson with exposure;
   * weighted linear regression with offsets against its exact Gaussian posterior;
@@ -25,8 +25,8 @@ from test_weights_sim import (HLOG, LIN, LOG, NB, POIS, check_edge_matrix, engin
                               thetas)
 
 pytestmark = pytest.mark.gpu
-GEOMETRIES = ((1, 2), (1, 16))
-COLUMNS = {2: 100, 16: 1000}
+GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
+COLUMNS = {2: 100, 4: 200, 8: 400, 16: 1000}
 
 
 def short_run(e, theta):
@@ -97,8 +97,8 @@ def test_weight_sets_on_device(gpu, geometry):
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("geometry", GEOMETRIES)
 @pytest.mark.parametrize("fma", [0, 1])
-def test_poisson_exposure_edges_against_high_precision(gpu, geometry, fma):
-    check_edge_matrix(None, POIS, geometry, fma)
+def test_poisson_exposure_edges_against_high_precision(gpu, geometry, fma, record_property):
+    record_property("max_error_over_bound", check_edge_matrix(None, POIS, geometry, fma))
 
 
 def mcse_mean(z):  # [C, S]: per-chain means are independent; their spread gives the standard error

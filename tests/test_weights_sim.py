@@ -27,8 +27,8 @@ from test_datasets_sim import compare_blocks, drive, drop_in, flat  # noqa: E402
 LIN, LOG, POIS, NB, LSIG, HLOG = hw.LIN, hw.LOG, hw.POIS, hw.NB, hw.LSIG, hw.HLOG
 MODELS = (LIN, LOG, POIS, NB, LSIG, HLOG)
 IDS = ["linear", "logistic", "poisson", "negbin", "linear_sigma", "hier_logistic"]
-GEOMETRIES = ((1, 2), (1, 16))
-COLUMNS = {2: 5, 16: 40}  # columns of x: one wavefront per chain, with padding
+GEOMETRIES = ((1, 2), (1, 4), (1, 8), (1, 16))
+COLUMNS = {2: 5, 4: 70, 8: 150, 16: 40}  # columns of x: one wavefront per chain, with padding
 GROUPS = 3
 COMBOS = ("offset", "weights", "both")
 
@@ -130,8 +130,8 @@ def check_edge_matrix(lib, model, geometry, fma):
 @pytest.mark.parametrize("model", MODELS, ids=IDS)
 @pytest.mark.parametrize("geometry", GEOMETRIES)
 @pytest.mark.parametrize("fma", [0, 1])
-def test_against_high_precision(sim, model, geometry, fma):
-    check_edge_matrix(sim, model, geometry, fma)
+def test_against_high_precision(sim, model, geometry, fma, record_property):
+    record_property("max_error_over_bound", check_edge_matrix(sim, model, geometry, fma))
 
 
 # ---- trailing zero weights are truncation ---------------------------------------------------------------------------

@@ -76,7 +76,7 @@ constexpr int kHeldWaves = 8;
 #elif defined(WN_ONLY_MEM_NW)
 #define WN_FOR_EACH_GEOMETRY(X)
 #elif defined(WN_SIM_GEOMETRIES)  // tests/cpusim: a cross-section (the headline's (1, 16) and its neighbours included)
-#define WN_FOR_EACH_GEOMETRY(X) X(1, 2) X(1, 4) X(2, 2) X(1, 16) X(2, 8) X(4, 4) X(8, 8)
+#define WN_FOR_EACH_GEOMETRY(X) X(1, 2) X(1, 4) X(1, 8) X(2, 2) X(1, 16) X(2, 8) X(4, 4) X(8, 8)
 #elif defined(WN_FAST_BUILD)
 #define WN_FOR_EACH_GEOMETRY(X) X(1, 2) X(4, 4) X(2, 8) X(1, 16) X(4, 8) X(8, 8) X(2, 16) X(4, 16)
 #else
