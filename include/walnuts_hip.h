@@ -159,7 +159,11 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
  * u_0 (num_groups) | .. | u_{Q-1} (num_groups) | s_0 .. s_{Q-1}], model_params = [prior variances (P) | 1 (Q num_groups,
  * reserved) | sigma_0 .. sigma_{Q-1}], P = num_params - Q (num_groups + 1) =
  * wn_model_data_columns_varying(model, num_params, num_groups, num_varying); at Q = 1 such a model is its hier_* sibling,
- * bit for bit.  The count models refuse a y that is not a finite non-negative integer (`config`).
+ * bit for bit.  A GROUPED model WITH A SCALE PARAMETER (kUsesGroups + kScaleParam: hier_linear_regression_sigma 35,
+ * hier_linear_regression_sigma_centered 36, walnuts_amd/csrc/models/hier_scale_glm.h) ends theta with TWO log scales:
+ * theta = [beta (P) | u (num_groups) | s_tau | s], tau = exp(s_tau) the group scale and exp(s) the noise sigma;
+ * model_params = [prior variances (P) | 1 (num_groups, reserved) | sigma_tau | sigma_0]; P = num_params - num_groups - 2.
+ * The count models refuse a y that is not a finite non-negative integer (`config`).
  * MANY datasets at once (one model, one prior): with obs_offsets != NULL, dataset g is rows [obs_offsets[g],
  * obs_offsets[g + 1]) of x, y and group (from 0, strictly increasing; datasets may differ in size; num_groups is shared
  * and a dataset may leave groups empty), and chain c is conditioned on dataset c / k, k = num_chains / num_datasets
@@ -330,9 +334,16 @@ WALNUTS_HIP_EXPORT void wn_default_config(wn_config* cfg);
 WALNUTS_HIP_EXPORT int wn_model_id(const char* name);
 /* The number of columns of x that a data model reads at num_params (and, for a grouped model, num_groups): num_params
  * for the flat models, num_params - 1 for a model with a scale parameter (kScaleParam: neg_binomial_regression,
- * linear_regression_sigma), num_params - num_groups - 1 for a grouped model.  -> -1 for an id no data model holds, and
- * for a grouped model with num_groups < 1. */
+ * linear_regression_sigma), num_params - num_groups - 1 for a grouped model, num_params - num_groups - 2 for a grouped
+ * model with a scale parameter (hier_linear_regression_sigma*).  -> -1 for an id no data model holds, and for a
+ * grouped model with num_groups < 1. */
 WALNUTS_HIP_EXPORT int wn_model_data_columns(int model, int num_params, int num_groups);
+/* How many trailing coordinates of theta are the log of a scale of the likelihood (kScaleParam) rather than a column
+ * of x or a group term: 1 for neg_binomial_regression, linear_regression_sigma and hier_linear_regression_sigma*, 0
+ * for every other model.  (The group scale log tau of a grouped model is not counted: every grouped model has it.)
+ * With it a caller splits num_params of a grouped model without guessing: num_groups = num_params - P - 1 -
+ * wn_model_num_scale_params(model).  -> -1 for an id that holds no model. */
+WALNUTS_HIP_EXPORT int wn_model_num_scale_params(int model);
 /* The same with num_varying (wn_observations): num_params - Q (num_groups + 1) for a model with varying slopes, Q =
  * num_varying (0 meaning 1); for every other model wn_model_data_columns' answer when num_varying <= 1.  -> -1 where
  * wn_engine_create_observed would refuse the numbers: num_varying > 1 for a model without varying slopes, Q outside
@@ -384,7 +395,8 @@ WALNUTS_HIP_EXPORT int wn_engine_create(wn_engine** out, int model, int num_para
  * seeded with chain_offset = g * k; the pooled statistics below keep their meaning (all chains), the _datasets ones are
  * per dataset.  `config` errors: obs == NULL; a data model created through wn_engine_create; data for a model without
  * kUsesData; a grouped model without `group`, and `group` for a model without kUsesGroups; num_params != P + num_groups
- * + 1 with P >= 1 and num_groups >= 1; num_varying > 1 for a model without kVaryingSlopes, and for a model with it
+ * + 1 (+ 2 for a grouped model with a scale parameter) with P >= 1 and num_groups >= 1; num_varying > 1 for a model
+ * without kVaryingSlopes, and for a model with it
  * num_varying outside [0, 8], num_params != P + Q (num_groups + 1) with P >= 1 and num_groups >= 1, or Q - 1 > P (Q =
  * num_varying, 0 meaning 1; the messages name the numbers); num_datasets < 1, num_chains not a multiple of it, offsets not from 0 or not
  * strictly increasing; non-finite data; a group outside [0, num_groups); a non-finite offset; a weight that is negative

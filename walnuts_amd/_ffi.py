@@ -107,6 +107,7 @@ SYMBOLS = [
     ("wn_internal_philox_probe", _i32, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _sz, _i32]),
     ("wn_model_data_columns", _i32, [_i32, _i32, _i32]),
     ("wn_model_data_columns_varying", _i32, [_i32, _i32, _i32, _i32]),
+    ("wn_model_num_scale_params", _i32, [_i32]),
     ("wn_internal_reference_normals", None, [C.c_uint, C.c_uint, _sz, _sz, _i32, _dbl, _dp]),
     ("walnutpie_ess", _i32, [_dp, _i32, _i32, C.POINTER(C.c_int), _i32, _dp, _errpp]),
     ("walnutpie_r_hat", _i32, [_dp, _i32, _i32, C.POINTER(C.c_int), _i32, _dp, _errpp]),

@@ -19,11 +19,12 @@ def _is_grouped(data) -> bool:
         return False
 
 
-def _block(data, num_params: int, cols: int, varying: int = 1):
+def _block(data, num_params: int, cols: int, varying: int = 1, scales: int = 0):
     """One block of observations as contiguous arrays (x, y, group, J).  A pair (x, y): x (num_obs, cols) float64, y
     (num_obs,) float64, group None, J 0.  A triple (x, y, group) of a grouped model (kUsesGroups): x (num_obs, P), group
-    (num_obs,) int32 and J = (num_params - P) / varying - 1, varying = Q the number of coefficients that vary by group
-    (kVaryingSlopes; 1: J = num_params - P - 1); a remainder is refused here, and the engine checks J >= 1, P >= 1,
+    (num_obs,) int32 and J = (num_params - P - scales) / varying - 1, varying = Q the number of coefficients that vary by
+    group (kVaryingSlopes; 1: J = num_params - P - 1 - scales) and scales = wn_model_num_scale_params(model), the
+    trailing log scales of the likelihood (0 or 1); a remainder is refused here, and the engine checks J >= 1, P >= 1,
     Q - 1 <= P and the range."""
     grouped = _is_grouped(data)
     if grouped:
@@ -51,14 +52,14 @@ def _block(data, num_params: int, cols: int, varying: int = 1):
         raise ValueError(f"data group must hold integers, got dtype {g.dtype}")
     if g.size and (g.min() < np.iinfo(np.int32).min or g.max() > np.iinfo(np.int32).max):
         raise ValueError("every group must be in [0, num_groups)")
-    rest = num_params - x.shape[1]
+    rest = num_params - x.shape[1] - scales
     if rest % varying != 0:
         raise ValueError(f"num_params - P must be a multiple of varying (num_params == P + varying * (J + 1)), got "
                          f"num_params {num_params}, P {x.shape[1]}, varying {varying}")
     return x, y, np.ascontiguousarray(g, dtype=np.int32), rest // varying - 1
 
 
-def _blocks(datasets, num_params: int, cols: int, varying: int = 1):
+def _blocks(datasets, num_params: int, cols: int, varying: int = 1, scales: int = 0):
     """Several datasets [(x0, y0), ...] or [(x0, y0, group0), ...] as one block, stacked in order: (x, y, group, J) as
     _block gives them, and int64 offsets [G + 1] (dataset g = rows offsets[g] .. offsets[g + 1])."""
     try:
@@ -71,7 +72,7 @@ def _blocks(datasets, num_params: int, cols: int, varying: int = 1):
     if any(_is_grouped(d) != grouped for d in items):
         raise ValueError("datasets must be all (x, y) pairs or all (x, y, group) triples")
     try:
-        parts = [_block(d, num_params, cols, varying) for d in items]
+        parts = [_block(d, num_params, cols, varying, scales) for d in items]
     except TypeError:
         if grouped:
             raise
@@ -139,12 +140,14 @@ def observations(lib, model: int, num_params: int, data=None, datasets=None, off
     # pair (x, y) for a grouped model) with its own message.
     cols = int(lib.wn_model_data_columns(int(model), int(num_params), 0))
     cols = cols if cols >= 0 else int(num_params)
+    # a grouped model's trailing log scales of the likelihood (hier_scale_glm.h): they say how num_params splits into P, J
+    scales = max(0, int(lib.wn_model_num_scale_params(int(model))))
     obs = _ffi.Observations()
     if datasets is not None:
-        x, y, group, J, offsets = _blocks(datasets, num_params, cols, varying)
+        x, y, group, J, offsets = _blocks(datasets, num_params, cols, varying, scales)
         obs.obs_offsets, obs.num_datasets = offsets.ctypes.data_as(_ffi._i64p), offsets.size - 1
     else:
-        x, y, group, J = _block(data, num_params, cols, varying)
+        x, y, group, J = _block(data, num_params, cols, varying, scales)
         offsets = None
         obs.num_obs = y.size
     obs.num_varying = varying   # (the engine refuses varying > 1 for a model without varying slopes)

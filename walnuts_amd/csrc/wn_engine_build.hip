@@ -31,8 +31,8 @@ void check_model_inputs(const wn::ModelOps& ops, int num_params, const double* m
     throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
   if (ops.uses_groups && data != nullptr && data->group == nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads a group per observation: create it with "
-                                "wn_engine_create_observed (x [num_obs][num_params - num_groups - 1], y, group "
-                                "[num_obs] in [0, num_groups))");
+                                "wn_engine_create_observed (x [num_obs][num_params - num_groups - " +
+                                std::string(ops.scale_param ? "2" : "1") + "], y, group [num_obs] in [0, num_groups))");
   if (!ops.uses_groups && data != nullptr && data->group != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
   if (ops.host_params_varying == nullptr && data != nullptr && data->num_varying > 1)
@@ -132,6 +132,16 @@ ObservationPlan plan_observations(const wn::ModelOps& ops, int num_params, size_
                                   "got num_varying " + std::to_string(Q) + ", P " + std::to_string(P));
     plan.cols = static_cast<int>(P);
     plan.num_varying = Q;
+  } else if (ops.uses_groups && ops.scale_param) {
+    // theta ends with two log scales: the group scale and the family's (models/hier_scale_glm.h)
+    const int J = data->num_groups;
+    const long long P = static_cast<long long>(num_params) - J - 2;
+    if (J < 1 || P < 1)
+      throw std::invalid_argument("a grouped model with a scale parameter needs num_params == P + num_groups + 2 with P >= 1 "
+                                  "and num_groups >= 1, got num_params " + std::to_string(num_params) + ", num_groups " +
+                                  std::to_string(J));
+    plan.cols = static_cast<int>(P);
+    plan.num_varying = 1;
   } else if (ops.uses_groups) {
     const int J = data->num_groups;
     if (J < 1 || num_params - J - 1 < 1)
@@ -441,8 +451,15 @@ int wn_model_data_columns(int model, int num_params, int num_groups) {
   if (model < 0 || model >= wn::kMaxModels) return -1;
   const wn::ModelOps* ops = wn::model_table()[model];
   if (ops == nullptr || !ops->uses_data) return -1;
-  if (ops->uses_groups) return num_groups >= 1 ? num_params - num_groups - 1 : -1;
+  if (ops->uses_groups) return num_groups >= 1 ? num_params - num_groups - (ops->scale_param ? 2 : 1) : -1;
   return ops->scale_param ? num_params - 1 : num_params;
+}
+
+int wn_model_num_scale_params(int model) {
+  if (model < 0 || model >= wn::kMaxModels) return -1;
+  const wn::ModelOps* ops = wn::model_table()[model];
+  if (ops == nullptr) return -1;
+  return ops->scale_param ? 1 : 0;
 }
 
 int wn_model_data_columns_varying(int model, int num_params, int num_groups, int num_varying) {

@@ -40,6 +40,12 @@ MODEL_HIER_POISSON_REGRESSION, MODEL_HIER_POISSON_REGRESSION_CENTERED = 27, 28
 # (ids 29-31 stay free: the tests place run-time models of their own there)
 MODEL_HIER_LINEAR_REGRESSION_SLOPES, MODEL_HIER_LOGISTIC_REGRESSION_SLOPES = 32, 33
 MODEL_HIER_POISSON_REGRESSION_SLOPES = 34
+# hierarchical regression with varying intercepts by group and an estimated scale
+# (walnuts_amd/csrc/models/hier_scale_glm.h): hier_linear_regression_sigma(_centered) is the multilevel normal model
+# y ~ N(x . beta + a_g, sigma) with sigma = exp(s) unknown.  theta = [beta (P) | group effects (J) | log tau | s],
+# params = [prior variances of beta (P) | 1 (J, reserved) | sigma_tau | sigma_0, the half-normal scale of exp(s)],
+# data = (x, y, group) with x of P = num_params - J - 2 columns
+MODEL_HIER_LINEAR_REGRESSION_SIGMA, MODEL_HIER_LINEAR_REGRESSION_SIGMA_CENTERED = 35, 36
 _dp = _ffi._dp
 
 
@@ -73,7 +79,8 @@ class DeviceEngine:
         """`data=(x, y)`: the observations of a model conditioned on data (wn_model_api.h kUsesData), x of shape
         (num_obs, dim) and y of shape (num_obs,); copied to the device once.  `data=(x, y, group)` for a grouped model
         (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
-        [0, J) with J = dim - P - 1.  `varying=Q` (MODEL_HIER_*_SLOPES, 1 <= Q <= 8, Q - 1 <= P): the intercept and
+        [0, J) with J = dim - P - 1 (J = dim - P - 2 for MODEL_HIER_LINEAR_REGRESSION_SIGMA*, whose theta ends with log tau
+        and the log scale s).  `varying=Q` (MODEL_HIER_*_SLOPES, 1 <= Q <= 8, Q - 1 <= P): the intercept and
         the slopes of the first Q - 1 columns of x vary by group, J = (dim - P) / Q - 1.  A model with a scale parameter
         (MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA) takes x of shape (num_obs, dim - 1): its last
         coordinate is s, not a column of x.  The count models (MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION,
