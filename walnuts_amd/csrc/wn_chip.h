@@ -514,10 +514,8 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
       v[2 * k + 1] = t[1];
     }
   }
-  // the moving end (always set 0 when a pool-resident span is merged) against a span end kept in the pool.  With 16
-  // elements per lane the two operands are taken half a vector at a time: the kernel is at its register limit there,
-  // and 64 more live registers mean as many moves to and from the accumulator file.  Both operands in LDS -- the usual
-  // case -- is decided by ONE test in front of the loads.
+  // the moving end (always set 0 when a pool-resident span is merged) against a span end kept in the pool.  Both
+  // operands in LDS -- the usual case -- is decided by ONE test in front of the loads.
   template <bool LDS_ONLY, int CH>
   __device__ __forceinline__ void pool_operands(int b, int j0, double (&v)[CH]) {
     if constexpr (LDS_ONLY) {
@@ -533,32 +531,58 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
       pool_load_slots<CH>(b, j0, v);
     }
   }
-  template <bool LDS_ONLY>
-  __device__ __forceinline__ void uturn_pool_partials(int bth, int brh, double& p_hot, double& p_far) {
+  // With 16 elements per lane the operands come as two halves (pool_operands: one tier test per half).  Both halves'
+  // loads are issued before the first half's arithmetic, each half into registers of its own -- live only here, where
+  // the leaf pair's temporaries are dead; nothing of this crosses a leaf loop --: ONE round trip to the pool stands in
+  // the open per test instead of two.  `issued()` runs behind the loads' issue: the caller's scalar work that the
+  // addresses do not depend on.  The sums are taken in the order j = 0 .. EPL-1 whatever the halves.
+  // (The compiler joins the LDS and the arena form of the arithmetic behind the loads into one block and guards it with
+  // the more careful of their counts: the generated code waits ONCE, for 13 of the 16 loads, not per consumed pair.
+  // What overlaps the round trip is therefore the caller's work in `issued()` and behind it, not the first pairs'
+  // arithmetic; keeping the two forms' arithmetic apart costs the headline kernel registers it does not have.)
+  // A model that holds a parameter vector in registers (2 * EPL of them) has no room for the second half: its kernel
+  // already keeps state in the accumulator file, and 64 more live registers doubled the moves to and from it (config #2's
+  // kernel: +2.7 % per step).  It takes the halves one after the other, as before.
+  static constexpr bool kPoolHalvesInFlight = !Model::kUsesParams;
+  template <bool LDS_ONLY, class Issued>
+  __device__ __forceinline__ void uturn_pool_partials(int bth, int brh, double& p_hot, double& p_far, Issued&& issued) {
     constexpr int CH = EPL >= 16 ? EPL / 2 : EPL;
+    constexpr int NH = kPoolHalvesInFlight ? EPL / CH : 1;  // halves loaded at once
     p_hot = 0.0;
     p_far = 0.0;
 #pragma unroll
-    for (int h = 0; h < EPL / CH; ++h) {
-      double a[CH], b[CH];
-      pool_operands<LDS_ONLY, CH>(bth, h * CH, a);
-      pool_operands<LDS_ONLY, CH>(brh, h * CH, b);
+    for (int h0 = 0; h0 < EPL / CH; h0 += NH) {
+      double a[NH][CH], b[NH][CH];
 #pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        const int jj = h * CH + j;
-        const double sd = im[jj] * (th[0][jj] - a[j]);
-        p_hot = mad(rh[0][jj], sd, p_hot);
-        p_far = mad(b[j], sd, p_far);
+      for (int h = 0; h < NH; ++h) {
+        pool_operands<LDS_ONLY, CH>(bth, (h0 + h) * CH, a[h]);
+        pool_operands<LDS_ONLY, CH>(brh, (h0 + h) * CH, b[h]);
       }
+      if (h0 == 0) issued();
+#pragma unroll
+      for (int h = 0; h < NH; ++h) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+          const int jj = (h0 + h) * CH + j;
+          const double sd = im[jj] * (th[0][jj] - a[h][j]);
+          p_hot = mad(rh[0][jj], sd, p_hot);
+          p_far = mad(b[h][j], sd, p_far);
+        }
+      }
+    }
+  }
+  // the two sums of the test against the span end in pool buffers (bth, brh), still to be reduced (turned_packed)
+  template <class Issued>
+  __device__ __forceinline__ void uturn_pool_sums(int bth, int brh, double& p_hot, double& p_far, Issued&& issued) {
+    if (WN_LIKELY(bth < n_lds && brh < n_lds)) {
+      uturn_pool_partials<true>(bth, brh, p_hot, p_far, issued);
+    } else {
+      uturn_pool_partials<false>(bth, brh, p_hot, p_far, issued);
     }
   }
   __device__ __forceinline__ bool uturn_pool(int bth, int brh, bool fwd) {
     double p_hot, p_far;
-    if (WN_LIKELY(bth < n_lds && brh < n_lds)) {
-      uturn_pool_partials<true>(bth, brh, p_hot, p_far);
-    } else {
-      uturn_pool_partials<false>(bth, brh, p_hot, p_far);
-    }
+    uturn_pool_sums(bth, brh, p_hot, p_far, [] {});
     return turned_packed(p_hot, p_far, fwd);
   }
   // the two sums' reduction and the test, one wavefront per chain: read off the compare's lane mask
@@ -848,23 +872,32 @@ struct TrajChip : TrajBase<TrajChip<Model, NW, EPL, WARM, FMA>, Model, NW> {
             --sp;
             int s_in_th, s_in_rh, s_sel;
             double s_w, s_lpsel;
-            this->stack_read(sp, s_in_th, s_in_rh, s_sel, s_w, s_lpsel);
+            // the test's loads need the two buffer indices of the entry only: the rest of the pop stands behind them
+            const int s_packed = this->stack_buffers(sp, s_in_th, s_in_rh);
             WN_PHASE(kPhUturn);
-            if (WN_UNLIKELY(uturn_pool(s_in_th, s_in_rh, fwd))) {  // walnuts.hpp:490-492
-              ok = false;
-              break;
-            }
-            WN_PHASE(kPhCombine);
+            double p_hot, p_far;
+            uturn_pool_sums(s_in_th, s_in_rh, p_hot, p_far, [&] { this->stack_scalars(sp, s_packed, s_sel, s_w, s_lpsel); });
+            // The merge's decision does not depend on the test: it stands in front of the branch, in the shadow of the
+            // test's loads and reduction.  A test that turns ends the extension WITHOUT taking the draw
+            // (walnuts.hpp:490-492): the draw is looked at here and taken behind the branch.
             const double total = uni(s_w + c_w);
-            const bool update = this->uniform01_ready() * total < c_w;
+            const bool update = this->uniform01_peek() * total < c_w;
             const int n_sel = update ? c_sel : s_sel;
             const double n_lpsel = update ? c_lpsel : s_lpsel;
             // The merged span keeps the older span's inner end and one of the two selections; what goes back to the
             // pool: the newer span's inner momentum, its inner position unless that is the selection kept, and the
             // selection not kept -- the older span's stays if it is that span's inner end.  (An index of the newer
             // span can be symbolic -- a leaf still in its register set -- and has no bit.)
-            free_mask |= Base::pool_bit(c_in_rh) | (c_in_th != n_sel ? Base::pool_bit(c_in_th) : 0ull) |
-                         (update ? (s_sel != s_in_th ? (1ull << s_sel) : 0ull) : Base::pool_bit(c_sel));
+            const unsigned long long freed =
+                Base::pool_bit(c_in_rh) | (c_in_th != n_sel ? Base::pool_bit(c_in_th) : 0ull) |
+                (update ? (s_sel != s_in_th ? (1ull << s_sel) : 0ull) : Base::pool_bit(c_sel));
+            if (WN_UNLIKELY(turned_packed(p_hot, p_far, fwd))) {  // walnuts.hpp:490-492
+              ok = false;
+              break;
+            }
+            WN_PHASE(kPhCombine);
+            this->take_draw();
+            free_mask |= freed;
             c_in_th = s_in_th;
             c_in_rh = s_in_rh;
             c_sel = n_sel;

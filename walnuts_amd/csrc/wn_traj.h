@@ -189,10 +189,18 @@ struct TrajBase {
     weight = lane_value(stk_d, 2 * sp);
     lpsel = lane_value(stk_d, 2 * sp + 1);
   }
-  __device__ __forceinline__ void stack_buffers(int sp, int& in_th, int& in_rh) const {
+  // a pop in two parts: the span's inner end (what the loads of its U-turn test are addressed by) -> the entry's packed
+  // indices, for stack_scalars to take the rest from
+  __device__ __forceinline__ int stack_buffers(int sp, int& in_th, int& in_rh) const {
     const int packed = lane_value(stk_i, sp);
     in_th = (packed & 127) - 2;
     in_rh = ((packed >> 7) & 127) - 2;
+    return packed;
+  }
+  __device__ __forceinline__ void stack_scalars(int sp, int packed, int& sel, double& weight, double& lpsel) const {
+    sel = (packed >> 14) - 2;
+    weight = lane_value(stk_d, 2 * sp);
+    lpsel = lane_value(stk_d, 2 * sp + 1);
   }
   int err;
   // (`err` also carries kNoteExtensionFailed: the failure channel of device models, wn_params.h -- set where an
@@ -464,6 +472,11 @@ struct TrajBase {
     ++n_draw;
     return lane_value(draw_u, j - draw_base);
   }
+  // the same draw looked at without being taken (a merge decides in front of a test that may end the extension, and an
+  // extension that ends there has not taken its draw: walnuts.hpp:490-492), and taken afterwards
+  // (as uniform01_ready: the register backend only, behind an ensure_draws() that covers the draw)
+  __device__ __forceinline__ double uniform01_peek() const { return lane_value(draw_u, uni(n_draw) - draw_base); }
+  __device__ __forceinline__ void take_draw() { ++n_draw; }
 
   // ---- span weights: combine (walnuts.hpp:368-387) in the linear domain ---------------------------------------------
   // The reference carries LOG weights: a leaf's is its joint log density, a merged span's the log_sum_exp of its halves
