@@ -14,6 +14,8 @@
  *   - the autocovariance is the direct sum  acov[t] = (1/N) sum_n (y[n]-ybar)(y[n+t]-ybar)  that the reference's
  *     zero-padded FFT evaluates (summary.hpp:55-73; its own test checks the FFT against exactly this direct form,
  *     tests/summary_test.cpp:610-627,681-693).  Eigen::FFT (kissfft) is not in /root/reference.
+ * Where it differs in RULE: quantiles order NaNs last whatever their sign bit (the reference's std::sort with `<` is
+ * undefined once a column holds a NaN, :505-506); everything else propagates IEEE arithmetic as the reference's code.
  * Pinned by the reference's known answers: tests/summary_test.cpp (means/variances :248-345, quantiles :534-568,
  * autocovariance :644-679, R-hat :825-880, ESS/MCSE :1073-1085,1117-1132,1182-1192) -> tests/test_summary_oracle.py
  * through tests/golden/summary_reference.json.
@@ -213,7 +215,9 @@ void quantiles(const Chains& c, const double* probs, size_t K, double* out /*[K]
   const double n_minus_1 = static_cast<double>(static_cast<int64_t>(c.N) - 1);
   for (size_t d = 0; d < c.D; ++d) {
     for (size_t i = 0; i < c.N; ++i) col[i] = c.x[i * c.D + d];
-    std::sort(col.begin(), col.end());
+    // the usual order of doubles with every NaN last (a strict weak order, which plain `<` is not once a NaN is
+    // present): the reference's std::sort (:505-506) is undefined there, so the rule is the project's
+    std::sort(col.begin(), col.end(), [](double a, double b) { return a < b || (b != b && a == a); });
     for (size_t k = 0; k < K; ++k) {
       const double h = probs[k] * n_minus_1;
       const int64_t lo = static_cast<int64_t>(std::floor(h));

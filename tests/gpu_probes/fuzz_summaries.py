@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU probe: randomised bit-exact campaign of the device posterior summaries against the summary oracle -- random
 numbers of ragged chains, dimensions (both the one-pass two-columns-per-lane moments and the column loops), chain
-lengths, autocorrelations, ties and quantile probabilities.
+lengths, autocorrelations, ties, quantile probabilities and, in a quarter of the cases, NaN and infinite draws.
    python tests/gpu_probes/fuzz_summaries.py [--seconds T] [--seed S]"""
 import argparse
 import os
@@ -28,9 +28,17 @@ def random_case(rng):
         for c in chains:
             z = c == 0
             c[z] = np.where(rng.uniform(size=int(z.sum())) < 0.5, -0.0, 0.0)
+    nonfinite = 0
+    if rng.uniform() < 0.25:             # non-finite draws under the stated rule: IEEE propagation in the
+        nonfinite = int(rng.integers(1, 6))   # moments as in the oracle, NaNs of either sign last in the quantiles
+        for _ in range(nonfinite):
+            c = chains[int(rng.integers(C))]
+            c[int(rng.integers(c.shape[0])), int(rng.integers(D))] = rng.choice(
+                [np.nan, np.copysign(np.nan, -1.0), np.inf, -np.inf])
     probs = tuple(sorted(set([float(p) for p in rng.uniform(0, 1, size=int(rng.integers(1, 9)))] + ([0.0, 1.0] if rng.uniform() < 0.3 else []))))
     total = sum(lens) * D
-    return chains, probs, dict(C=C, D=D, max_len=max(lens), min_len=min(lens), probs=len(probs), full_acov=total < 400000)
+    return chains, probs, dict(C=C, D=D, max_len=max(lens), min_len=min(lens), probs=len(probs), nonfinite=nonfinite,
+                               full_acov=total < 400000)
 
 
 def main():

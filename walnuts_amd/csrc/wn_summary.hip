@@ -13,7 +13,8 @@
 //     are computed on demand until every dimension has stopped -- typically one or two passes over the draws.
 //   * quantiles: instead of sorting every column (:505-506), a radix select on the order-preserving 64-bit image
 //     of the doubles, 4 bits per pass, for all requested order statistics of all dimensions at once: 16 passes
-//     over the draws, LDS-private histograms (lane = dimension: no intra-wave conflicts), exact.
+//     over the draws, LDS-private histograms (lane = dimension: no intra-wave conflicts), exact.  NaNs of either sign
+//     share the largest key: they order last, as numpy.sort has them (the reference's sort is undefined there).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -317,6 +318,7 @@ static __global__ void geyer_kernel(int D, int min_len, int avail, int first, co
 
 // ---- quantiles: radix select ---------------------------------------------------------------------------------
 static __device__ __forceinline__ unsigned long long order_key(double x) {
+  if (x != x) return ~0ull;  // every NaN, whatever its sign bit, is the largest key: NaNs order last
   unsigned long long u;
   __builtin_memcpy(&u, &x, sizeof(u));
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // ascending doubles <-> ascending unsigned keys
