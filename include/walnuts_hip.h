@@ -436,6 +436,27 @@ WALNUTS_HIP_EXPORT int wn_engine_log_lik(wn_engine* e, const double* theta, size
  * errors: as wn_engine_log_lik; chains->dims != num_params; num_chains not a multiple of G; chains on another device. */
 WALNUTS_HIP_EXPORT int wn_engine_log_predictive(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, double* lpd,
                                                 double* mean, double* var, int64_t* count, WalnutpyError** err);
+/* PSIS-LOO from draws that stay on the device: leave-one-out cross-validation by Pareto-smoothed importance sampling,
+ * without a refit.  For every row n, over the S draws of the chains that belong to the row's block (ordered as for
+ * wn_engine_log_predictive, blocks and row_mask likewise), with the ratios' logarithms r = -l_n(theta) - max(-l_n):
+ *   the M = min(floor(S / 5), ceil(3 sqrt(S))) largest ratios are replaced by the quantiles of a generalised Pareto
+ *   distribution fitted to them (Zhang and Stephens 2009, as the R package loo fits it; M < 5 or a degenerate tail: no
+ *   smoothing) and cut at the largest raw ratio;
+ *   elpd_loo[n] = log(sum w exp l_n / sum w) with the smoothed weights w,  pareto_k[n] = the fitted shape (+inf without
+ *   a fit; above 0.7 the estimate is not to be trusted),  ess[n] = 1 / sum of the squared normalised weights (NO
+ *   autocorrelation correction),  lpd[n] = log mean exp l_n,  count[n] = S.
+ * csrc/wn_psis.h states the algorithm and every order of summation; the result is a function of the inputs alone (not
+ * of launch or workspace sizes).  The [rows][S] matrix of l is built in a device workspace of workspace_bytes (0: 1 GiB)
+ * a slab of rows at a time -- a multiple of 64 rows, 64 at least -- and never reaches the host.  A column that holds a
+ * non-finite l gives NaN four times; a masked row NaN and count 0.  `config` errors: as wn_engine_log_predictive; a block
+ * of more than 1 864 135 draws (its tail of more than 4 096 is sorted on chip: thin the chains). */
+WALNUTS_HIP_EXPORT int wn_engine_psis_loo(wn_engine* e, wn_chains* chains, const uint8_t* row_mask, size_t workspace_bytes,
+                                          double* elpd_loo, double* pareto_k, double* ess, double* lpd, int64_t* count,
+                                          WalnutpyError** err);
+/* (internal, tests) the matrix of wn_engine_psis_loo for block `dataset`, out [rows][num_draws] (host); a `config` error
+ * unless the block's chains hold num_draws draws */
+WALNUTS_HIP_EXPORT int wn_internal_psis_matrix(wn_engine* e, wn_chains* chains, int dataset, size_t num_draws, double* out,
+                                               WalnutpyError** err);
 /* PREDICTIONS of a data model, the sibling of wn_engine_log_lik: for position t and row n of dataset `dataset`,
  *   eta_out[t][n] = the linear predictor (x_n . beta, the group effect, the offset: as the likelihood forms it),
  *   mean_out[t][n] = E[y | theta_t, x_n],   var_out[t][n] = Var[y | theta_t, x_n]

@@ -17,6 +17,6 @@ from .engine import (MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_LINEAR_REGRESSION, M
 from .device import WalnutsOutputArray, WarmupInfo, walnuts_device  # noqa: F401
 from . import models, summary  # noqa: F401,E402
 from .summary import MarkovChains, Summarizer  # noqa: F401,E402
-from .pointwise import PointwisePredictive, kfold_elpd, log_predictive  # noqa: F401,E402
+from .pointwise import PointwisePredictive, PsisLoo, kfold_elpd, log_predictive, psis_loo  # noqa: F401,E402
 from .predict import Prediction, predict, predict_draws  # noqa: F401,E402
 from .replicate import PredictiveCheck, posterior_predictive_check, replicate_draws  # noqa: F401,E402

@@ -130,6 +130,8 @@ SYMBOLS = [
     ("wn_engine_eval", _i32, [_vp, _dp, _dp, _dp, _errpp]),
     ("wn_engine_log_lik", _i32, [_vp, _dp, _sz, _i32, _dp, _errpp]),
     ("wn_engine_log_predictive", _i32, [_vp, _vp, C.POINTER(C.c_uint8), _dp, _dp, _dp, _i64p, _errpp]),
+    ("wn_engine_psis_loo", _i32, [_vp, _vp, C.POINTER(C.c_uint8), _sz, _dp, _dp, _dp, _dp, _i64p, _errpp]),
+    ("wn_internal_psis_matrix", _i32, [_vp, _vp, _i32, _sz, _dp, _errpp]),
     ("wn_engine_predict", _i32, [_vp, _dp, _sz, _i32, _dp, _dp, _dp, _errpp]),
     ("wn_engine_predict_fold", _i32, [_vp, _vp, C.POINTER(C.c_uint8), _dp, _dp, _dp, _dp, _dp, _i64p, _errpp]),
     ("wn_engine_predict_chains", _i32, [_vp, _vp, _i32, _i32, C.POINTER(_vp), _errpp]),

@@ -174,7 +174,8 @@ inline int padded_dim(const Geometry& g, int dim) {
 // writing its header and a three-line .hip file ("Adding a device model").
 // The pointwise log-likelihood of a data model that declares the hook (wn_model_api.h, kPointwise; wn_pointwise.h)
 struct PointwiseOps {
-  // log_lik / the per-chain fold of the predictive pass (pointwise_kernel), one wavefront per work item
+  // log_lik / the per-chain fold of the predictive pass / the matrix of PSIS-LOO (pointwise_kernel), one wavefront per
+  // work item
   void (*launch)(const Geometry&, int grid, hipStream_t, bool fma, const PointwiseParams&);
   // the across-chain merge of the predictive pass (pointwise_combine_kernel)
   void (*launch_combine)(int grid, hipStream_t, const PointwiseCombineParams&);
@@ -238,7 +239,7 @@ inline std::string& registry_error() {
   return msg;
 }
 // Everything a separately compiled model and the library must agree on: the layout of what crosses the boundary.
-constexpr int kModelAbiVersion = 17;
+constexpr int kModelAbiVersion = 18;
 struct ModelAbi {
   int version;
   unsigned sizeof_ops, sizeof_params, sizeof_geometry;

@@ -5,6 +5,8 @@
 //   log_lik      theta [T][D] at positions the caller chose           -> l [T][N]            (wn_engine_log_lik)
 //   predictive   a wn_chains block [C][max_len][D], lengths respected -> per row n: lpd_n = log mean_t exp l_n(theta_t),
 //                mean_n and var_n of l_n(theta_t) over the draws, their count            (wn_engine_log_predictive)
+//   matrix       the same block -> l [N][ld], a row's draws in one contiguous column, in a device workspace
+//                (stage 1 of wn_engine_psis_loo: wn_psis.h)
 //
 // The row term is the model's own (wn_model_api.h, kPointwise): Model::pointwise() streams a TILE of 64 consecutive rows,
 // forms eta in the order models/glm.h states (slot-order Cx::mad dot product, wave_sum_packed butterfly, group effect,
@@ -22,6 +24,8 @@
 //                for row n0 + k; the chain's partial (m, s, mean, M2) goes to a workspace laid out [4][chains][rows].
 //                pointwise_combine_kernel (one thread per row) then merges the partials of a block's chains IN CHAIN
 //                ORDER into a running state and, after the last chain, writes lpd, mean, var and count.
+//   matrix:      item = (chain c, tile), the predictive walk without the fold: the term of the chain's draw i is stored,
+//                lane k -> l[n0 + k][draw0[c] + i], draw0[c] the draws of the block's chains before c.
 // Rows a mask switches off are not evaluated: a pair of rows that is off issues no load, a tile that is all off no draw.
 //
 // THE FOLD (draws ordered by chain, then by iteration; arithmetic independent of the engine's arithmetic mode:
@@ -63,7 +67,7 @@ constexpr int kPointwiseCombineBlock = 64;
 struct PointwiseParams {
   Observations obs;         // the engine's observation block (all datasets / the shared rows)
   const double* row_const;  // [rows of the block]: c_n(y_n), beside y
-  int32_t dim, predictive;
+  int32_t dim, predictive;  // predictive: 0 log_lik, 1 (kPointwiseFold) the fold, 2 (kPointwiseMatrix) the matrix
   // the block of rows this launch evaluates: data rows [row0, row0 + num_rows) of obs
   int64_t row0;
   int32_t num_rows, num_tiles;
@@ -79,7 +83,11 @@ struct PointwiseParams {
   int32_t chain0, slab_chains;
   const uint8_t* mask;
   double* partial;
+  // matrix: out [num_rows][ld]; draw0 [chains of the chains block]: the column of chain c's first draw
+  const long long* draw0;
+  int64_t ld;
 };
+constexpr int kPointwiseFold = 1, kPointwiseMatrix = 2;
 
 // What Model::pointwise sees as `cx`: the data-model calls of wn_model_api.h over ONE block of rows (row indices are
 // relative to the block), one wavefront.  P: the kernel's parameter struct -- obs, dim, row0, num_rows are read
@@ -201,6 +209,15 @@ __global__ __launch_bounds__(64) void pointwise_kernel(const PointwiseParams Q) 
     // (a tile without a live row folds nothing: its partial is never read)
     int any = 0;
     for (int k = 0; k < kPointwiseTile; ++k) any |= lane_value(live ? 1 : 0, k);
+    if (Q.predictive == kPointwiseMatrix) {
+      double* column = Q.out + (row ? n0 + me : 0) * Q.ld + Q.draw0[chain];
+      for (int i = 0; any && i < len; ++i) {
+        cx.load_theta(draw + static_cast<long long>(i) * Q.dim, th);
+        const double l = Model::template pointwise<EPL>(cx, th, n0, live) + c;
+        if (live) column[i] = l;
+      }
+      continue;
+    }
     if (any) {
       for (int i = 0; i < len; ++i) {
         cx.load_theta(draw + static_cast<long long>(i) * Q.dim, th);

@@ -267,6 +267,34 @@ class DeviceEngine:
                    mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp), count.ctypes.data_as(_ffi._i64p))
         return lpd, mean, var, count
 
+    def psis_loo(self, chains, row_mask=None, *, workspace_bytes: int = 0):
+        """(elpd_loo, pareto_k, ess, lpd, count) per row from draws that stay on the device (wn_engine_psis_loo):
+        leave-one-out cross-validation by Pareto-smoothed importance sampling.  Blocks, shapes and `row_mask` as for
+        log_predictive; a masked row gives NaN four times and count 0.  pareto_k is +inf where no tail could be fitted;
+        ess is 1 / sum of the squared normalised weights, with no autocorrelation correction.  `workspace_bytes`: the
+        device memory the rows-by-draws matrix may take at a time (0: 1 GiB); it changes no value.
+        walnuts_amd.psis_loo wraps this."""
+        shape = self._rows() if not self._weight_sets else (self.num_datasets, self._row_sizes[0])
+        mask = None
+        if row_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(row_mask) != 0, dtype=np.uint8)
+            if mask.shape != tuple(shape):
+                raise ValueError(f"row_mask must have shape {tuple(shape)}, got {mask.shape}")
+        elpd, k, ess, lpd = (np.empty(shape) for _ in range(4))
+        count = np.empty(shape, dtype=np.int64)
+        self._call(self.lib.wn_engine_psis_loo, chains._h,
+                   None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), int(workspace_bytes),
+                   elpd.ctypes.data_as(_dp), k.ctypes.data_as(_dp), ess.ctypes.data_as(_dp), lpd.ctypes.data_as(_dp),
+                   count.ctypes.data_as(_ffi._i64p))
+        return elpd, k, ess, lpd, count
+
+    def _psis_matrix(self, chains, num_draws: int, dataset: int = 0):
+        """(tests) stage 1 of psis_loo alone: the [rows, num_draws] matrix of block `dataset`, whose chains hold
+        num_draws draws (wn_internal_psis_matrix)"""
+        out = np.empty((self._rows(int(dataset)), int(num_draws)))
+        self._call(self.lib.wn_internal_psis_matrix, chains._h, int(dataset), int(num_draws), out.ctypes.data_as(_dp))
+        return out
+
     def predict(self, theta, dataset: int = 0):
         """(eta, mean, var), each [T, N]: the linear predictor, E[y | theta, x_n] and Var[y | theta, x_n] of every row of
         dataset `dataset` at positions theta [T, D] (wn_engine_predict), in the engine's arithmetic mode.  eta is formed

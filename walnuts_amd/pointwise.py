@@ -143,3 +143,87 @@ def kfold_elpd(model: int, views, *, num_params: int, data, weight_sets, offset=
     fold = np.argmax(held, axis=0)
     cols = np.arange(ws.shape[1])
     return PointwisePredictive(res.lpd[fold, cols], res.mean[fold, cols], res.var[fold, cols], res.count[fold, cols])
+
+
+@dataclass
+class PsisLoo:
+    """Per row: elpd_loo = the PSIS estimate of log p(y_n | y_-n), pareto_k = the shape of the generalised Pareto fitted
+    to the row's largest importance ratios (+inf: no tail could be fitted), ess = 1 / sum of the squared normalised
+    weights -- draws are counted as independent: there is NO autocorrelation (r_eff) correction --, lpd = log mean
+    exp l_n over the draws, count = draws.  Rows that were not evaluated (masked out) hold NaN and count 0 and take no
+    part below."""
+    elpd_loo: np.ndarray
+    pareto_k: np.ndarray
+    ess: np.ndarray
+    lpd: np.ndarray
+    count: np.ndarray
+
+    @property
+    def evaluated(self) -> np.ndarray:
+        return self.count > 0
+
+    @property
+    def elpd(self) -> float:
+        """Sum of elpd_loo over the evaluated rows: the expected log pointwise predictive density."""
+        return float(np.sum(self.elpd_loo[self.evaluated]))
+
+    @property
+    def se(self) -> float:
+        """Standard error of elpd: sqrt(n * sample variance of elpd_loo over the n evaluated rows)."""
+        v = self.elpd_loo[self.evaluated]
+        return float(np.sqrt(v.size * np.var(v, ddof=1))) if v.size > 1 else float("nan")
+
+    @property
+    def p_loo(self) -> float:
+        """Effective number of parameters: the sum over rows of lpd - elpd_loo."""
+        on = self.evaluated
+        return float(np.sum(self.lpd[on] - self.elpd_loo[on]))
+
+    @property
+    def looic(self) -> float:
+        """-2 elpd, on the deviance scale."""
+        return -2.0 * self.elpd
+
+    @property
+    def num_bad(self) -> int:
+        """Rows with pareto_k > 0.7: their elpd_loo is not to be trusted (refit without the row, or K-fold)."""
+        return int(np.sum(self.pareto_k[self.evaluated] > 0.7))
+
+
+def psis_loo(model: int, chains, *, num_params: int, data=None, datasets=None, offset=None, cfg=None,
+             lib_path: Optional[str] = None, varying: int = 1, weight_sets=None) -> PsisLoo:
+    """PSIS-LOO of a fit from draws that stay on the device: elpd_loo, pareto_k, ess, lpd and count per row (PsisLoo).
+
+    `chains`, `data=`, `datasets=`, `offset=` and `varying` as for ``log_predictive``: one MarkovChains of G * k chains,
+    block g scored on dataset g, or a sequence of G MarkovChains.  `weight_sets=` is refused: the weights of a weighted
+    fit are not part of a row's importance ratio (for K refits use ``kfold_elpd``).  Model parameters are not needed."""
+    if weight_sets is not None:
+        raise ValueError("psis_loo takes no weight_sets: the weights of a weighted fit are not part of a row's importance "
+                         "ratio, so the draws of such a fit cannot be reweighted to leave a row out (kfold_elpd scores K "
+                         "refits)")
+    if isinstance(chains, MarkovChains):
+        blocks = None
+    else:
+        blocks = list(chains)
+        if not blocks or not all(isinstance(b, MarkovChains) for b in blocks):
+            raise ValueError("chains must be a MarkovChains or a sequence of MarkovChains (one per block)")
+    G = len(list(datasets)) if datasets is not None else 1
+    common = dict(cfg=cfg, params=_ones(num_params), lib_path=lib_path, varying=varying)
+    if blocks is None:
+        e = DeviceEngine(model, num_params, G, data=data, datasets=datasets, offset=offset, **common)
+        try:
+            return PsisLoo(*e.psis_loo(chains))
+        finally:
+            e.close()
+    if len(blocks) != G:
+        raise ValueError(f"{len(blocks)} blocks of chains for {G} datasets")
+    items = [data] if datasets is None else list(datasets)
+    offs = [offset] if datasets is None else ([None] * G if offset is None else list(offset))
+    parts = []
+    for g in range(G):
+        e = DeviceEngine(model, num_params, 1, data=items[g], offset=offs[g], **common)
+        try:
+            parts.append(e.psis_loo(blocks[g]))
+        finally:
+            e.close()
+    return PsisLoo(*(np.concatenate([p[i] for p in parts]) for i in range(5)))
