@@ -163,6 +163,11 @@ WALNUTS_HIP_EXPORT int walnutpie_sample_device_resident(
  * hier_linear_regression_sigma_centered 36, walnuts_amd/csrc/models/hier_scale_glm.h) ends theta with TWO log scales:
  * theta = [beta (P) | u (num_groups) | s_tau | s], tau = exp(s_tau) the group scale and exp(s) the noise sigma;
  * model_params = [prior variances (P) | 1 (num_groups, reserved) | sigma_tau | sigma_0]; P = num_params - num_groups - 2.
+ * VARYING SLOPES WITH A SCALE PARAMETER (kVaryingSlopes + kScaleParam: hier_linear_regression_slopes_sigma 40,
+ * walnuts_amd/csrc/models/hier_slopes_scale_glm.h), y ~ x + (1 + x_0 + .. | g) with noise sigma = exp(s): theta =
+ * [beta (P) | u_0 (num_groups) | .. | u_{Q-1} (num_groups) | s_0 .. s_{Q-1} | s], model_params = [prior variances (P) |
+ * 1 (Q num_groups, reserved) | sigma_0 .. sigma_{Q-1} | sigma_0 of exp(s)], P = num_params - Q (num_groups + 1) - 1; at
+ * Q = 1 it is hier_linear_regression_sigma, bit for bit.
  * The count models refuse a y that is not a finite non-negative integer (`config`).
  * MANY datasets at once (one model, one prior): with obs_offsets != NULL, dataset g is rows [obs_offsets[g],
  * obs_offsets[g + 1]) of x, y and group (from 0, strictly increasing; datasets may differ in size; num_groups is shared
@@ -335,17 +340,17 @@ WALNUTS_HIP_EXPORT int wn_model_id(const char* name);
 /* The number of columns of x that a data model reads at num_params (and, for a grouped model, num_groups): num_params
  * for the flat models, num_params - 1 for a model with a scale parameter (kScaleParam: neg_binomial_regression,
  * linear_regression_sigma), num_params - num_groups - 1 for a grouped model, num_params - num_groups - 2 for a grouped
- * model with a scale parameter (hier_linear_regression_sigma*).  -> -1 for an id no data model holds, and for a
- * grouped model with num_groups < 1. */
+ * model with a scale parameter (hier_linear_regression_sigma*, and hier_linear_regression_slopes_sigma, for which this
+ * is the answer at num_varying = 1).  -> -1 for an id no data model holds, and for a grouped model with num_groups < 1. */
 WALNUTS_HIP_EXPORT int wn_model_data_columns(int model, int num_params, int num_groups);
 /* How many trailing coordinates of theta are the log of a scale of the likelihood (kScaleParam) rather than a column
- * of x or a group term: 1 for neg_binomial_regression, linear_regression_sigma and hier_linear_regression_sigma*, 0
- * for every other model.  (The group scale log tau of a grouped model is not counted: every grouped model has it.)
+ * of x or a group term: 1 for neg_binomial_regression, linear_regression_sigma, hier_linear_regression_sigma* and
+ * hier_linear_regression_slopes_sigma, 0 for every other model.  (The group scale log tau of a grouped model is not counted: every grouped model has it.)
  * With it a caller splits num_params of a grouped model without guessing: num_groups = num_params - P - 1 -
  * wn_model_num_scale_params(model).  -> -1 for an id that holds no model. */
 WALNUTS_HIP_EXPORT int wn_model_num_scale_params(int model);
 /* The same with num_varying (wn_observations): num_params - Q (num_groups + 1) for a model with varying slopes, Q =
- * num_varying (0 meaning 1); for every other model wn_model_data_columns' answer when num_varying <= 1.  -> -1 where
+ * num_varying (0 meaning 1), less wn_model_num_scale_params(model); for every other model wn_model_data_columns' answer when num_varying <= 1.  -> -1 where
  * wn_engine_create_observed would refuse the numbers: num_varying > 1 for a model without varying slopes, Q outside
  * [1, 8], num_groups < 1, fewer than one column, or Q - 1 above the number of columns. */
 WALNUTS_HIP_EXPORT int wn_model_data_columns_varying(int model, int num_params, int num_groups, int num_varying);

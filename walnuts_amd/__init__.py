@@ -13,6 +13,7 @@ from .engine import (MODEL_DIAG_NORMAL, MODEL_FUNNEL, MODEL_LINEAR_REGRESSION, M
                      MODEL_HIER_POISSON_REGRESSION_CENTERED, MODEL_HIER_LINEAR_REGRESSION_SLOPES,
                      MODEL_HIER_LOGISTIC_REGRESSION_SLOPES, MODEL_HIER_POISSON_REGRESSION_SLOPES, MODEL_LINEAR_REGRESSION_SIGMA, MODEL_NEG_BINOMIAL_REGRESSION,
                      MODEL_HIER_LINEAR_REGRESSION_SIGMA, MODEL_HIER_LINEAR_REGRESSION_SIGMA_CENTERED,
+                     MODEL_HIER_LINEAR_REGRESSION_SLOPES_SIGMA,
                      MODEL_POISSON_REGRESSION, MODEL_RW1, MODEL_STD_NORMAL, DeviceEngine, model_id, default_config, stream_version)
 from .device import WalnutsOutputArray, WarmupInfo, walnuts_device  # noqa: F401
 from . import models, summary  # noqa: F401,E402

@@ -54,8 +54,9 @@ def _block(data, num_params: int, cols: int, varying: int = 1, scales: int = 0):
         raise ValueError("every group must be in [0, num_groups)")
     rest = num_params - x.shape[1] - scales
     if rest % varying != 0:
-        raise ValueError(f"num_params - P must be a multiple of varying (num_params == P + varying * (J + 1)), got "
-                         f"num_params {num_params}, P {x.shape[1]}, varying {varying}")
+        minus, plus = (f" - {scales}", f" + {scales}") if scales else ("", "")
+        raise ValueError(f"num_params - P{minus} must be a multiple of varying (num_params == P + varying * (J + 1){plus}), "
+                         f"got num_params {num_params}, P {x.shape[1]}, varying {varying}")
     return x, y, np.ascontiguousarray(g, dtype=np.int32), rest // varying - 1
 
 

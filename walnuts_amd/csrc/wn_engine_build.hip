@@ -31,8 +31,11 @@ void check_model_inputs(const wn::ModelOps& ops, int num_params, const double* m
     throw std::invalid_argument(std::string(ops.name) + " model reads no data (it does not declare kUsesData)");
   if (ops.uses_groups && data != nullptr && data->group == nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads a group per observation: create it with "
-                                "wn_engine_create_observed (x [num_obs][num_params - num_groups - " +
-                                std::string(ops.scale_param ? "2" : "1") + "], y, group [num_obs] in [0, num_groups))");
+                                "wn_engine_create_observed (x [num_obs][num_params - " +
+                                std::string(ops.scale_param && ops.host_params_varying != nullptr
+                                                ? "num_varying * (num_groups + 1) - 1"
+                                                : ops.scale_param ? "num_groups - 2" : "num_groups - 1") +
+                                "], y, group [num_obs] in [0, num_groups))");
   if (!ops.uses_groups && data != nullptr && data->group != nullptr)
     throw std::invalid_argument(std::string(ops.name) + " model reads no groups (it does not declare kUsesGroups)");
   if (ops.host_params_varying == nullptr && data != nullptr && data->num_varying > 1)
@@ -46,7 +49,7 @@ void check_model_inputs(const wn::ModelOps& ops, int num_params, const double* m
 // The shape of a checked observation block, as the upload and the monitors need it (all defaults without data)
 struct ObservationPlan {
   int cols = 0;          // columns of x: num_params, num_params - 1 for a model with a scale parameter, or
-                         // P = num_params - Q (J + 1) for a grouped model
+                         // P = num_params - Q (J + 1) for a grouped model (less 1 with a scale parameter as well)
   int num_varying = 0;   // Q of a grouped model: coefficients that vary by group (1 without kVaryingSlopes)
   size_t total_obs = 0;  // rows of the observation block
   int weight_sets = 1;   // W weight vectors over the one shared block, an engine of W datasets above the kernels
@@ -118,14 +121,17 @@ ObservationPlan plan_observations(const wn::ModelOps& ops, int num_params, size_
   plan.weighted = data->weight != nullptr;
   if (ops.uses_groups && ops.host_params_varying != nullptr) {
     // varying slopes: Q coefficients vary by group, 0 meaning 1 (the intercept only)
+    // (with a scale parameter theta ends with one more log scale, the family's: models/hier_slopes_scale_glm.h)
     const int J = data->num_groups, Q = data->num_varying == 0 ? 1 : data->num_varying;
-    const long long P = static_cast<long long>(num_params) - static_cast<long long>(Q) * (static_cast<long long>(J) + 1);
+    const long long P = static_cast<long long>(num_params) - static_cast<long long>(Q) * (static_cast<long long>(J) + 1) -
+                        (ops.scale_param ? 1 : 0);
     if (Q < 1 || Q > wn::kMaxVaryingCoefficients)
       throw std::invalid_argument("a model with varying slopes needs 1 <= num_varying <= " +
                                   std::to_string(wn::kMaxVaryingCoefficients) + ", got " + std::to_string(data->num_varying));
     if (J < 1 || P < 1)
-      throw std::invalid_argument("a model with varying slopes needs num_params == P + num_varying * (num_groups + 1) with "
-                                  "P >= 1 and num_groups >= 1, got num_params " + std::to_string(num_params) +
+      throw std::invalid_argument("a model with varying slopes needs num_params == P + num_varying * (num_groups + 1) " +
+                                  std::string(ops.scale_param ? "+ 1 " : "") +
+                                  "with P >= 1 and num_groups >= 1, got num_params " + std::to_string(num_params) +
                                   ", num_groups " + std::to_string(J) + ", num_varying " + std::to_string(Q));
     if (Q - 1 > P)
       throw std::invalid_argument("the varying slopes belong to the first num_varying - 1 columns of x: num_varying - 1 <= P, "
@@ -469,7 +475,8 @@ int wn_model_data_columns_varying(int model, int num_params, int num_groups, int
   if (ops->host_params_varying == nullptr) return num_varying > 1 ? -1 : wn_model_data_columns(model, num_params, num_groups);
   const int Q = num_varying == 0 ? 1 : num_varying;
   if (Q < 1 || Q > wn::kMaxVaryingCoefficients || num_groups < 1) return -1;
-  const long long P = static_cast<long long>(num_params) - static_cast<long long>(Q) * (static_cast<long long>(num_groups) + 1);
+  const long long P = static_cast<long long>(num_params) - static_cast<long long>(Q) * (static_cast<long long>(num_groups) + 1) -
+                      (ops->scale_param ? 1 : 0);
   return P >= 1 && Q - 1 <= P ? static_cast<int>(P) : -1;
 }
 

@@ -26,8 +26,6 @@ static_assert(!(kUsesData && kHasStreaming), "a data model has no streaming form
 static_assert(!uses_groups<WN_MODEL_TYPE>::value || kUsesData, "kUsesGroups needs kUsesData (wn_model_api.h)");
 static_assert(!scale_param<WN_MODEL_TYPE>::value || kUsesData, "kScaleParam needs kUsesData (wn_model_api.h)");
 static_assert(!uses_row_terms<WN_MODEL_TYPE>::value || kUsesData, "kUsesRowTerms needs kUsesData (wn_model_api.h)");
-static_assert(!(scale_param<WN_MODEL_TYPE>::value && varying_slopes<WN_MODEL_TYPE>::value),
-              "kScaleParam and kVaryingSlopes do not combine (wn_model_api.h)");
 static_assert(!varying_slopes<WN_MODEL_TYPE>::value || uses_groups<WN_MODEL_TYPE>::value,
               "kVaryingSlopes needs kUsesGroups (wn_model_api.h)");
 static constexpr bool geometry_built(int nw) { return !kUsesData || nw == 1; }

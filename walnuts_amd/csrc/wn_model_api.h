@@ -75,11 +75,13 @@
 //     // host_params(params, num_params, num_varying), which is called in place of the two-argument form.
 //     // wn_engine_create refuses num_varying > 1 for a model without this member.  models/hier_slopes_glm.h.
 //     static constexpr bool kVaryingSlopes = true;
-//     // ... or, on top of kUsesData and NOT with kVaryingSlopes (a static_assert), a SCALE PARAMETER as the last
+//     // ... or, on top of kUsesData, a SCALE PARAMETER as the last
 //     // coordinate: x has P = num_params - 1 columns, stored at the flat stride Dp with column num_params - 1 zero, so
 //     // the row pass never sees the scale (host_data's last argument is P).  models/glm_scale.h.  Together with
 //     // kUsesGroups theta ends [.. | s_tau | s]: x has P = num_params - J - 2 columns at the grouped stride, so neither
-//     // scale is ever a column (wn_model_num_scale_params tells a front end).  models/hier_scale_glm.h.
+//     // scale is ever a column (wn_model_num_scale_params tells a front end).  models/hier_scale_glm.h.  Together with
+//     // kVaryingSlopes theta ends [.. | s_0 .. s_{Q-1} | s]: x has P = num_params - Q (J + 1) - 1 columns, and
+//     // host_params(params, num_params, num_varying) sees Q + 1 trailing scales.  models/hier_slopes_scale_glm.h.
 //     static constexpr bool kScaleParam = true;
 //     // ... and, on top of kUsesData, per-row OFFSETS and WEIGHTS (wn_observations::offset / weight /
 //     // num_weight_sets; each optional at run time): the model reads them through cx.has_offset() / obs_offset() /
@@ -170,14 +172,15 @@
 //
 // Registration is a five-line translation unit, wn_kernels_<name>.hip, that the Makefile picks up by its name:
 //   #include "models/my_model.h"
-//   #define WN_MODEL_ID 6                 // 0-5, 15-18, 24-28 and 32-36 are taken (std_normal, diag_normal, funnel, rw1,
+//   #define WN_MODEL_ID 6                 // 0-5, 15-18, 24-28, 32-36 and 40 are taken (std_normal, diag_normal, funnel, rw1,
 //                                         //   linear_regression, logistic_regression; hier_linear_regression,
 //                                         //   hier_logistic_regression and their _centered forms; poisson_regression,
 //                                         //   neg_binomial_regression, linear_regression_sigma,
 //                                         //   hier_poisson_regression and its _centered form;
 //                                         //   hier_linear_regression_slopes, hier_logistic_regression_slopes,
 //                                         //   hier_poisson_regression_slopes at 32-34;
-//                                         //   hier_linear_regression_sigma and its _centered form at 35, 36); < 64
+//                                         //   hier_linear_regression_sigma and its _centered form at 35, 36;
+//                                         //   hier_linear_regression_slopes_sigma at 40); < 64
 //   #define WN_MODEL_TAG my_model         // wn_model_id("my_model") finds it at run time
 //   #define WN_MODEL_TYPE wn::MyModel
 //   #include "wn_kernels.inc"
@@ -186,7 +189,8 @@
 // group channel (hierarchical regression with varying intercepts); models/hier_slopes_glm.h one with varying slopes on
 // top of it (32-34); models/glm_scale.h one with a scale parameter
 // (negative binomial regression, linear regression with an estimated noise level); models/hier_scale_glm.h one with
-// groups and a scale parameter (hierarchical linear regression with an estimated noise level, 35 and 36).
+// groups and a scale parameter (hierarchical linear regression with an estimated noise level, 35 and 36);
+// models/hier_slopes_scale_glm.h one with varying slopes and a scale parameter (40).
 #pragma once
 
 #include "wn_devmath.h"

@@ -9,6 +9,7 @@
 //   identity (unit noise)      eta                                     1
 //   linear_regression_sigma    eta                                     scale * scale,  scale = dexp(s)
 //   hier_linear_regression_sigma*   eta (with the group effect)        scale * scale,  scale = dexp(s), s the LAST coordinate
+//   hier_linear_regression_slopes_sigma   eta (with the group terms)   scale * scale,  scale = dexp(s), s the LAST coordinate
 //   logit                      eta >= 0 ? d : e * d                    (e * d) * d      e = dexp(-|eta|), d = 1 / (1 + e)
 //   log (Poisson)              dexp(eta)                               mu
 //   negative binomial          dexp(eta)                               Cx::mad(kappa * mu, mu, mu),  kappa = dexp(s)

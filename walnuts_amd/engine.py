@@ -46,6 +46,13 @@ MODEL_HIER_POISSON_REGRESSION_SLOPES = 34
 # params = [prior variances of beta (P) | 1 (J, reserved) | sigma_tau | sigma_0, the half-normal scale of exp(s)],
 # data = (x, y, group) with x of P = num_params - J - 2 columns
 MODEL_HIER_LINEAR_REGRESSION_SIGMA, MODEL_HIER_LINEAR_REGRESSION_SIGMA_CENTERED = 35, 36
+# varying intercepts and slopes by group AND an estimated noise level, non-centered
+# (walnuts_amd/csrc/models/hier_slopes_scale_glm.h): y ~ x + (1 + x_0 + .. | g) with sigma = exp(s) unknown, `varying=Q`
+# as for MODEL_HIER_*_SLOPES.  theta = [beta (P) | u_0 (J) | .. | u_{Q-1} (J) | log tau_0 .. log tau_{Q-1} | s], params =
+# [prior variances of beta (P) | 1 (Q J, reserved) | sigma_0 .. sigma_{Q-1} | sigma_0 of exp(s)], data = (x, y, group)
+# with P = num_params - Q (J + 1) - 1 columns; at varying=1 it is MODEL_HIER_LINEAR_REGRESSION_SIGMA, bit for bit
+# (ids 37 and 38 stay reserved for grouped negative binomial models, 39 stays free)
+MODEL_HIER_LINEAR_REGRESSION_SLOPES_SIGMA = 40
 _dp = _ffi._dp
 
 
@@ -81,7 +88,8 @@ class DeviceEngine:
         (kUsesGroups: MODEL_HIER_*): x of shape (num_obs, P), y and the integer group of shape (num_obs,), groups in
         [0, J) with J = dim - P - 1 (J = dim - P - 2 for MODEL_HIER_LINEAR_REGRESSION_SIGMA*, whose theta ends with log tau
         and the log scale s).  `varying=Q` (MODEL_HIER_*_SLOPES, 1 <= Q <= 8, Q - 1 <= P): the intercept and
-        the slopes of the first Q - 1 columns of x vary by group, J = (dim - P) / Q - 1.  A model with a scale parameter
+        the slopes of the first Q - 1 columns of x vary by group, J = (dim - P) / Q - 1 (J = (dim - P - 1) / Q - 1 for
+        MODEL_HIER_LINEAR_REGRESSION_SLOPES_SIGMA, whose theta ends with the log scale s).  A model with a scale parameter
         (MODEL_NEG_BINOMIAL_REGRESSION, MODEL_LINEAR_REGRESSION_SIGMA) takes x of shape (num_obs, dim - 1): its last
         coordinate is s, not a column of x.  The count models (MODEL_POISSON_REGRESSION, MODEL_NEG_BINOMIAL_REGRESSION,
         MODEL_HIER_POISSON_REGRESSION*) need every y to be a finite non-negative integer.
